@@ -11,10 +11,15 @@ before the timed region.  One step = one fpldpc_decode launch over the batch.
 Multi-GPU: one process per GPU (torchrun), rank r decodes frames [r*B, (r+1)*B) of the same
 stream (skip-ahead), no data-path collective; one all-reduce of the BER counters at the end.
 
-Prints ONE JSON line (rank 0) with roofline and cpu_baseline (the oracle's C restatement of
-decode_general_fp, one core, timed on this host; calibrated against the reference's own decoder in
-the newest profiles/r*/cpu_calibration.json, tools/cpu_calibrate.py, carried as
-cpu_baseline.calibration).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up,
+times --steps launches, writes the last step's outputs when --dump-outputs is given, and prints the
+line with the roofline (arithmetic on the timed launches and committed counters, no run of its own).
+--full adds every other measurement and check, each after the timed region: the parity sample
+against the CPU oracle, cpu_baseline (the oracle's C restatement of decode_general_fp, one core,
+timed on this host; calibrated against the reference's own decoder in the newest
+profiles/r*/cpu_calibration.json, tools/cpu_calibrate.py, carried as cpu_baseline.calibration) and
+its all-cores leg, the host-to-device copy (h2d) and, with --inflight-steps, two_in_flight.  Without
+--full those fields are null.
 
 roofline: the decoder keeps every message on chip (measured HBM traffic ~1/570 of an HBM-streaming
 decoder's bytes), so its binding bound is VALU issue: "achieved" = wave-level VALU instructions per
@@ -139,6 +144,29 @@ def calibration(cfg):
     return None
 
 
+DUMP_HARD_BYTES = 48 << 20  # of --dump-outputs' 64 MB in all, for the hard decisions
+
+
+def dump_outputs(path, n, hard_words, iters, ok, bit_err, totals, unpack_hard):
+    """--dump-outputs: what a caller of the timed decode holds after its last step, one
+    <name>.npy each (float32, the int64 counters float64): `hard` [frames][n] hard decisions (0/1)
+    of the frames listed in `hard_frames` (every frame while that fits DUMP_HARD_BYTES, else a
+    sorted sample drawn with the fixed SEED), and per frame of the whole batch `iters`,
+    `syndrome_ok` and `bit_errors`; `totals` = the accumulated {bit errors, frame errors, frames,
+    iterations} of the timed steps.  Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    batch = hard_words.shape[0]
+    rows = np.arange(batch)
+    if batch * n * 4 > DUMP_HARD_BYTES:
+        rows = np.sort(np.random.default_rng(SEED).choice(batch, DUMP_HARD_BYTES // (n * 4), replace=False))
+    arrays = {"hard": unpack_hard(hard_words[rows], n).astype(np.float32), "hard_frames": rows.astype(np.float32),
+              "iters": iters.astype(np.float32), "syndrome_ok": ok.astype(np.float32),
+              "bit_errors": bit_err.astype(np.float32), "totals": totals.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -187,22 +215,34 @@ def main():
                     help="untimed warm-up continues past --warmup steps until this much decode time has passed: "
                          "the GPU clock settles over the first tens of ms of a sustained decode (a 3-step warm-up "
                          "measured 1.5 %% below a 30-step one, profiles/r1/warmup)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the parity sample against "
+                         "the CPU oracle, the CPU baselines (see --no-cpu, --cpu-frames), the host-to-device copy and "
+                         "--inflight-steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0's frames) as DIR/<name>.npy: hard, "
+                         "hard_frames, iters, syndrome_ok, bit_errors, totals; the inputs are the same in every run "
+                         "with the same arguments")
     ap.add_argument("--config", choices=["A", "W", "R"], default="A")
     ap.add_argument("--batch", type=int, default=0, help="frames per GPU (default: 4096 A, 8192 W, 4096 R)")
     ap.add_argument("--ebn0", type=float, default=None)
     ap.add_argument("--cpu-frames", type=int, default=None,
-                    help="oracle frames timed for cpu_baseline (default: the A and W batches, 512 R frames: about 10 s on one core)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="with --full: oracle frames timed for cpu_baseline (default: the A and W batches, 512 R frames: "
+                         "about 10 s on one core)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend for N > 1 (gloo: rehearsal with ranks sharing one GPU)")
     ap.add_argument("--llr-fill", type=int, default=None,
                     help="diagnostic only: replace the channel LLRs by this constant (data-activity experiments)")
     ap.add_argument("--inflight-steps", type=int, default=0,
-                    help="steps of the supplementary two-batches-in-flight measurement (default 0: not run, so that "
-                         "a profile of the default command sees only the headline's launches)")
+                    help="with --full: steps of the supplementary two-batches-in-flight measurement (default 0: not run)")
     ap.add_argument("--decoder", choices=["fixed", "float"], default="fixed",
                     help="fixed: decode_general_fp (the headline); float: decode_general, double BP (SURVEY 8f row 3)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.inflight_steps > 0 and not args.full:
+        ap.error("--inflight-steps is a --full measurement")
     self_launch(args, sys.argv[1:])  # returns only in a rank (or at N = 1)
 
     import torch
@@ -298,7 +338,12 @@ def main():
     elapsed = t1 - t0
     launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
-    # Beside the headline (one batch at a time, each launch waiting for the last frame of the one
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else writes these buffers again
+        dumped = dump_outputs(args.dump_outputs, code.n, hard.cpu().numpy(), iters.cpu().numpy(), ok.cpu().numpy(),
+                              bit_err.cpu().numpy(), totals.cpu().numpy(), F.unpack_hard)
+
+    # --full, beside the headline (one batch at a time, each launch waiting for the last frame of the one
     # before): two decoders on two streams alternating over the same batches, as a caller that keeps
     # two batches in flight would run them -- the next launch's workgroups take the CUs that one
     # launch's tail leaves idle (its last frames, up to max_iter iterations, run alone on their CU).
@@ -306,7 +351,7 @@ def main():
     # checked equal to the headline's.  Reported as `two_in_flight`, never as `value`.
     inflight = None
     n_if = args.inflight_steps
-    if not fl and n_if > 0 and args.llr_fill is None:
+    if args.full and not fl and n_if > 0 and args.llr_fill is None:
         dec2 = F.Decoder(code, max_iter=max_iter, width_mask=mask, device=local)
         dec2.set_reference(np.arange(k_info, dtype=np.int32), np.zeros(k_info, np.uint8))
         st2 = [stream, torch.cuda.Stream(dev)]
@@ -342,10 +387,10 @@ def main():
                             "every step; not the headline"}
         del dec2, bufs
 
-    # the host->device copy of one batch of LLRs (pinned), timed separately; the
+    # --full, SURVEY 8(d): the host->device copy of one batch of LLRs (pinned), timed separately; the
     # PCIe-inclusive rate would be frames / (launch + copy) with no copy/compute overlap
     h2d = None
-    if rank == 0:
+    if args.full and rank == 0:
         pinned = torch.from_numpy(llr_host).pin_memory()
         dst = torch.empty_like(llr)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -367,7 +412,7 @@ def main():
     value = frames_total * k_info / t_max / 1e6
     avg_iters = tot[3] / max(tot[2], 1)
 
-    # Parity against the CPU oracle (the metric's "BER match") on a sample spread over the whole
+    # --full: parity against the CPU oracle (the metric's "BER match") on a sample spread over the whole
     # batch: every (batch / 192)-th frame plus the last 64, so it holds first fills of the persistent
     # grid, refills and the last frames pulled.  Then, at N = 1 only, the CPU baseline (the bench
     # contract's rule; at N > 1 the parity sample still runs on rank 0 while the other ranks wait on a
@@ -375,8 +420,8 @@ def main():
     # barrier).
     parity = parity_sample = None
     cpu = cpu_mt = None
-    wait_group = dist.new_group(backend="gloo") if pg and world > 1 else None
-    if rank == 0:
+    wait_group = dist.new_group(backend="gloo") if args.full and pg and world > 1 else None
+    if args.full and rank == 0:
         try:
             from oracle import oracle as O
             ocode = O.OracleCode.from_alist_text(code.write_alist())
@@ -519,6 +564,7 @@ def main():
             "value": round(value, 3),
             "unit": "Mb/s",
             "n_gpus": world,
+            "full": args.full,
             "steps": args.steps,
             "warmup": args.warmup,
             "warmup_steps_run": n_w,
@@ -543,6 +589,7 @@ def main():
             "ber": {"bit_errors": tot[0], "frame_errors": tot[1], "frames": tot[2], "avg_iters": round(avg_iters, 3)},
             "parity_vs_cpu_oracle": parity,
             "parity_sample": parity_sample,
+            "outputs_dumped": dumped,
             "collective": ({"backend": dist.get_backend(), "world": world, "ops": "all_reduce SUM int64[4] + MAX elapsed"}
                            if pg else None),
         }

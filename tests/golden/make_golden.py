@@ -13,6 +13,8 @@ Fixtures written (all small; tests read them, nothing reads /root/reference at t
   sxor_ff.npz         sxor(x, y) at FRAC 4 / mask 0xff: full table on [-96, 96]^2, 20000 sampled
                       pairs on [-4096, 4096]^2, SHA-256 of the full int32 table on [-1024, 1024]^2.
   codes.json          token-stream SHA-256 + dims of the three hot-path alist files.
+  g_files.npz         the two G files FP_Encoder(char*, int) reads (H_802.11_IndZerog.txt, codes/
+                      G_array_forward.txt), byte for byte (uint8; deflate brings 3.3 MB to 0.7 MB).
   kat_w.npz / .json   KAT-W: codeword + info positions/bits of ArrayLDPC_Debug_Wifi
                       (PerfTest.cpp:33-96), the published line (wifi_results_4_4_2dB_30iter.txt)
                       and the reference's cumulative (bit errors, frame errors) every 10000 frames.
@@ -178,6 +180,11 @@ def main():
         codes[key] = {"file": rel, "n": t[0], "m": t[1], "dv_max": t[2], "dc_max": t[3],
                       "tokens": len(t), "token_sha256": token_sha(t)}
     json.dump(codes, open(os.path.join(HERE, "codes.json"), "w"), indent=1)
+
+    # ---------------------------------------------------------------- G files (data, as they lie)
+    np.savez_compressed(os.path.join(HERE, "g_files.npz"),
+                        **{key: np.frombuffer(open(os.path.join(REF, rel), "rb").read(), np.uint8)
+                           for key, rel in (("W", "H_802.11_IndZerog.txt"), ("A", "codes/G_array_forward.txt"))})
 
     # ---------------------------------------------------------------- KAT-W inputs
     lines = run("codeword").splitlines()

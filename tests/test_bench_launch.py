@@ -31,8 +31,10 @@ def test_launch_command_in_place():
 
 
 def test_missing_gpus_fail_loudly():
-    # no HIP device here: --gpus 2 over RCCL must refuse (exit 2) before starting any rank
+    # no HIP device visible (none on a CPU machine; hidden from the child on a GPU machine, so that the
+    # test reads the same everywhere): --gpus 2 over RCCL must refuse (exit 2) before starting any rank
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = ""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 2, r.stderr

@@ -71,3 +71,34 @@ def test_committed_profile_is_of_the_shipped_build(F):
     if ids != {built}:
         pytest.skip(f"{os.path.relpath(newest, ROOT)} profiles kernel build {ids.pop()}, the in-tree library is {built}: "
                     "re-run tools/gpu_round.sh PHASE=prof before quoting a roofline fraction")
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files; the hard decisions whole while they fit the
+    byte budget, else the frames of a fixed (seeded) sorted sample, the same from run to run."""
+    import numpy as np
+    b = _bench()
+    n, batch = 70, 50
+    rs = np.random.default_rng(5)
+    words = rs.integers(-2**31, 2**31, (batch, 3), dtype=np.int64).astype(np.int32)
+    per = [rs.integers(0, 31, batch).astype(np.int32), rs.integers(0, 2, batch).astype(np.uint8),
+           rs.integers(0, n, batch).astype(np.int32)]
+    totals = np.array([2**40 + 1, 7, batch, 900], np.int64)
+    bits = np.unpackbits(words.view(np.uint8).reshape(batch, -1), axis=1, bitorder="little")[:, :n]
+
+    def unpack(w, nn):
+        return np.unpackbits(np.ascontiguousarray(w).view(np.uint8).reshape(len(w), -1), axis=1, bitorder="little")[:, :nn]
+
+    shapes = b.dump_outputs(str(tmp_path / "whole"), n, words, *per, totals, unpack)
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in shapes}
+    assert shapes["hard"] == [batch, n] and (got["hard"] == bits).all() and (got["hard_frames"] == np.arange(batch)).all()
+    assert (got["iters"] == per[0]).all() and (got["syndrome_ok"] == per[1]).all() and (got["bit_errors"] == per[2]).all()
+    assert got["totals"].dtype == np.float64 and got["totals"].tolist() == totals.tolist()
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != "totals")
+    monkeypatch.setattr(b, "DUMP_HARD_BYTES", 20 * n * 4 + 8)  # room for 20 frames
+    for d in ("s1", "s2"):
+        assert b.dump_outputs(str(tmp_path / d), n, words, *per, totals, unpack)["hard"] == [20, n]
+    s1, s2 = ({k: np.load(tmp_path / d / f"{k}.npy") for k in shapes} for d in ("s1", "s2"))
+    rows = s1["hard_frames"].astype(int)
+    assert len(set(rows)) == 20 and (np.diff(rows) > 0).all() and (s1["hard"] == bits[rows]).all()
+    assert (s1["iters"] == per[0]).all() and all((s1[k] == s2[k]).all() for k in shapes)

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REF_DIR
+from conftest import GOLDEN
 
 
 def _g(name):
@@ -41,12 +41,14 @@ def test_random_codewords_satisfy_h(F):
         assert (cw[:, enc.info_index] <= 1).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference G files only in the build container")
-def test_g_file_loader_matches_native(F):
-    """FP_Encoder(char*, int) (ArrayLDPC_Encoder.cpp:34-157) on the reference's own G files."""
-    for gfile, code in (("H_802.11_IndZerog.txt", F.Code.wifi_1944_r12()),
-                        ("codes/G_array_forward.txt", F.Code.array(47, 5))):
-        eg = F.Encoder.load_g(os.path.join(REF_DIR, gfile))
+def test_g_file_loader_matches_native(F, tmp_path):
+    """FP_Encoder(char*, int) (ArrayLDPC_Encoder.cpp:34-157) on the reference's own G files
+    (H_802.11_IndZerog.txt and codes/G_array_forward.txt, stored byte for byte in g_files.npz)."""
+    g = _g("g_files.npz")
+    for key, code in (("W", F.Code.wifi_1944_r12()), ("A", F.Code.array(47, 5))):
+        gfile = tmp_path / f"G_{key}.txt"
+        gfile.write_bytes(g[key].tobytes())
+        eg = F.Encoder.load_g(str(gfile))
         en = F.Encoder.from_code(code)
         assert (eg.info_index == en.info_index).all() and (eg.parity_index == en.parity_index).all()
         u = np.random.default_rng(1).integers(0, 2, (4, eg.k))

@@ -35,8 +35,9 @@ def test_bench_two_ranks_gloo(cfg, batch):
     carries the VALU-issue roofline fraction (the two ranks share the GPU: a lower fraction)."""
     steps = 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend",
-           "gloo", "--config", cfg, "--batch", str(batch), "--steps", str(steps), "--warmup", "1", "--no-cpu"]
+           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+           "--backend", "gloo", "--config", cfg, "--batch", str(batch), "--steps", str(steps), "--warmup", "1",
+           "--no-cpu"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT,
                        env={**os.environ, "OMP_NUM_THREADS": "4"})
     assert p.returncode == 0, p.stderr[-3000:]

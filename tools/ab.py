@@ -31,7 +31,7 @@ def main():
             for vname, venv in variants:
                 tag = f"{cname}_{vname}_{rep}"
                 t = time.time()
-                p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu", *cargs.split()],
+                p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu", *cargs.split()],
                                    env={**os.environ, **venv}, capture_output=True, text=True, timeout=300)
                 open(os.path.join(out, tag + ".err"), "w").write(p.stderr)
                 if p.returncode != 0:

@@ -18,7 +18,7 @@ for rep in $(seq 1 ${REPS:-2}); do
       envs=()
       [ -n "$vlib" ] && envs+=("FPLDPC_LIB_PATH=$vlib")
       [ -n "$venv" ] && IFS=',' read -r -a more <<< "$venv" && envs+=("${more[@]}")
-      env "${envs[@]}" timeout -k 10 300 python bench.py $cargs --no-cpu ${BENCH_ARGS} > "$OUT/${vname}_${cname}_$rep.json" 2> "$OUT/${vname}_${cname}_$rep.err" || exit $?
+      env "${envs[@]}" timeout -k 10 300 python bench.py --full $cargs --no-cpu ${BENCH_ARGS} > "$OUT/${vname}_${cname}_$rep.json" 2> "$OUT/${vname}_${cname}_$rep.err" || exit $?
     done
   done
 done

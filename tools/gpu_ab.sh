@@ -15,7 +15,7 @@ for rep in 1 2; do
   for cfg in ${CONFIGS:-A W R}; do
     for lv in ${LIBS:-new=}; do
       name=${lv%%=*}; path=${lv#*=}
-      FPLDPC_LIB_PATH=$path timeout -k 10 300 python bench.py --config $cfg --no-cpu ${BENCH_ARGS} > "$OUT/${name}_${cfg}_$rep.json" 2> "$OUT/${name}_${cfg}_$rep.err" || exit $?
+      FPLDPC_LIB_PATH=$path timeout -k 10 300 python bench.py --full --config $cfg --no-cpu ${BENCH_ARGS} > "$OUT/${name}_${cfg}_$rep.json" 2> "$OUT/${name}_${cfg}_$rep.err" || exit $?
     done
   done
 done

@@ -10,7 +10,7 @@ for r in ${RUNS:-base:0}; do
   spec=${r%%:*}; cap=${r##*:}; name=${spec%%=*}; lib=""; [ "$spec" != "$name" ] && lib=${spec#*=}
   tag=${name}_wg$cap
   export FPLDPC_LIB_PATH=$lib FPLDPC_FLOAT_WG_PER_CU=$cap
-  timeout -k 10 300 python bench.py --decoder float --steps 4 --warmup 1 --no-cpu > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" \
+  timeout -k 10 300 python bench.py --full --decoder float --steps 4 --warmup 1 --no-cpu > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" \
   && timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch_$tag" -o run -- python3 bench.py --decoder float --steps 2 --warmup 1 --no-cpu > /dev/null 2> "$OUT/fetch_$tag.err" \
   && timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write_$tag" -o run -- python3 bench.py --decoder float --steps 2 --warmup 1 --no-cpu > /dev/null 2> "$OUT/write_$tag.err" \
   || exit $?

@@ -15,7 +15,7 @@ run_tests() {
 run_tests \
 && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
 && for cfg in ${CFGS:-A}; do
-     timeout -k 10 300 python bench.py --config $cfg ${BENCH_ARGS} > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || exit $?
+     timeout -k 10 300 python bench.py --full --config $cfg ${BENCH_ARGS} > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || exit $?
      python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['config']['kernel'], d['parity_vs_cpu_oracle'])" "$OUT/bench_$cfg.json" $cfg
    done
 rc=$?

@@ -23,7 +23,7 @@ step_smoke() {
 step_bench() {
   has bench || return 0
   for cfg in ${CFGS:-A W R}; do
-    timeout -k 10 300 python bench.py --config $cfg ${BENCH_ARGS} > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || return $?
+    timeout -k 10 300 python bench.py --full --config $cfg ${BENCH_ARGS} > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || return $?
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['config']['kernel'], d['parity_vs_cpu_oracle'])" "$OUT/bench_$cfg.json" $cfg
   done
 }

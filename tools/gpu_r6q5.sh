@@ -8,7 +8,7 @@ FPLDPC_ALLOW_STALE_PROFILE=1 FPLDPC_PARAM_REPORT=$OUT/param_sweep.jsonl timeout 
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit 1
 for w in "A --config A" "W --config W" "R --config R" "W_2dB --config W --ebn0 2.0" "A_4.5dB --config A --ebn0 4.5"; do
   set -- $w; name=$1; shift
-  timeout -k 10 300 python bench.py "$@" --inflight-steps 30 > $OUT/bench_$name.json 2> $OUT/bench_$name.err || exit 1
+  timeout -k 10 300 python bench.py --full "$@" --inflight-steps 30 > $OUT/bench_$name.json 2> $OUT/bench_$name.err || exit 1
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['config']['kernel'].split()[0], d['parity_vs_cpu_oracle'], (d.get('two_in_flight') or {}).get('value'))" $OUT/bench_$name.json $name
 done
 SQ="SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU"

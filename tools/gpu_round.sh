@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 rocm-smi --showproductname > "$OUT/smi.txt" 2>&1 || true
 b() {  # b NAME ARGS... : one bench line
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
+  timeout -k 10 300 python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
 }
 SQ="SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE"
 SQF="SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_LDS SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"
