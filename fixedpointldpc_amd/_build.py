@@ -21,6 +21,9 @@ SOURCES = [
     "fpldpc_kernels_w1.hip",
     "fpldpc_gen.hip",
     "fpldpc_float.hip",
+    # the layered decoder: not in DEVICE_TUS / HASHED_TUS -- the build id covers the kernels with committed counters
+    "fpldpc_layered.cpp",
+    "fpldpc_layered.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

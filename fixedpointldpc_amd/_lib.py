@@ -101,6 +101,13 @@ def lib():
         "fpldpc_edge_ram_words": (ctypes.c_int, [P, ctypes.POINTER(I64)]),
         "fpldpc_decode_frame": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
         "fpldpc_decode_frame_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P]),
+        "fpldpc_code_layering": (ctypes.c_int, [P, I32, P]),
+        "fpldpc_layered_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, ctypes.POINTER(P)]),
+        "fpldpc_layered_destroy": (ctypes.c_int, [P]),
+        "fpldpc_layered_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
+        "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
+        "fpldpc_layered_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
+        "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
         "fpldpc_rng_skip": (I64, [I64, U64]),
         "fpldpc_channel_llr_host": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, P,
                                                    I32, I32]),
@@ -143,6 +150,8 @@ EXPORTED = [
     "fpldpc_encoder_dims", "fpldpc_encoder_info_index", "fpldpc_unpack_info_bytes", "fpldpc_encoder_encode_host",
     "fpldpc_encoder_free", "fpldpc_encoder_encode", "fpldpc_channel_llr",
     "fpldpc_decode_float", "fpldpc_decode_float_host",
+    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_destroy", "fpldpc_layered_describe",
+    "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
 ]
 
@@ -216,6 +225,12 @@ class Code:
         buf = ctypes.create_string_buffer(need.value + 1)
         _check(lib().fpldpc_code_write_alist(self._h, buf, need.value + 1, ctypes.byref(need)))
         return buf.value.decode()
+
+    def layering(self, layer_checks=0):
+        """(layer_checks used, layers) of the layered decoder (fpldpc_code_layering); 0 = auto."""
+        out = np.zeros(2, np.int32)
+        _check(lib().fpldpc_code_layering(self._h, layer_checks, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def syndrome_ok(self, bits):
         b = np.ascontiguousarray(bits, np.uint8)
@@ -384,6 +399,75 @@ class Decoder:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.fpldpc_decoder_destroy(self._h)
+            self._h = None
+
+
+class LayeredDecoder:
+    """fpldpc_layered_t: the layered (row-serial) schedule of the fixed-point decoder, batched on the
+    GPU.  layer_checks = 0 picks the layer size (Code.layering).  Same outputs as Decoder."""
+
+    def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
+                 layer_checks=0):
+        p = Params()
+        lib().fpldpc_params_default(ctypes.byref(p))
+        p.max_iter, p.frac_bits, p.width_mask = max_iter, frac_bits, width_mask
+        p.early_term, p.precheck, p.device = int(bool(early_term)), int(bool(precheck)), device
+        self.code = code
+        self.params = p
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_layered_create(code._h, ctypes.byref(p), layer_checks, ctypes.byref(h)))
+        self._h = h
+        self.hard_words = (code.n + 31) // 32
+
+    def describe(self):
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().fpldpc_layered_describe(self._h, buf, 256))
+        return buf.value.decode()
+
+    def set_reference(self, info_index, info_bits):
+        idx = np.ascontiguousarray(info_index, np.int32)
+        bits = np.ascontiguousarray(info_bits, np.uint8)
+        _check(lib().fpldpc_layered_set_reference(self._h, _ptr(idx), _ptr(bits), len(idx)))
+
+    def decode_ptrs(self, llr_ptr, llr_type, batch, hard=0, iters=0, syn_ok=0, post=0, bit_errors=0, totals=0,
+                    stream=0):
+        """Asynchronous decode on device pointers (ints); stream is a hipStream_t as int."""
+        c = ctypes.c_void_p
+        _check(lib().fpldpc_layered_decode(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
+                                           c(syn_ok or None), c(post or None), c(bit_errors or None),
+                                           c(totals or None), c(stream or None)))
+
+    decode_torch = Decoder.decode_torch  # the same tensor plumbing over this class's decode_ptrs
+
+    def decode_host(self, llr, post=None, bit_errors=False, totals=None):
+        """Synchronous decode of a host [B][n] int16/int32 array; returns numpy outputs (as Decoder.decode_host)."""
+        llr = np.ascontiguousarray(llr)
+        assert llr.ndim == 2 and llr.shape[1] == self.code.n and llr.dtype in (np.int16, np.int32)
+        B = llr.shape[0]
+        llr_type = FPLDPC_LLR_I16 if llr.dtype == np.int16 else FPLDPC_LLR_I32
+        hard = np.zeros((B, self.hard_words), np.uint32)
+        iters = np.zeros(B, np.int32)
+        ok = np.zeros(B, np.uint8)
+        post_arr = None
+        if post is not None:
+            post_arr = np.ascontiguousarray(post, np.int32) if not isinstance(post, bool) else np.zeros(
+                (B, self.code.n), np.int32)
+        be = np.zeros(B, np.int32) if bit_errors else None
+        tot = None if totals is None else np.ascontiguousarray(totals, np.int64)
+        _check(lib().fpldpc_layered_decode_host(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok),
+                                                _ptr(post_arr), _ptr(be), _ptr(tot)))
+        out = {"hard": hard, "iters": iters, "syndrome_ok": ok}
+        if post_arr is not None:
+            out["post"] = post_arr
+        if be is not None:
+            out["bit_errors"] = be
+        if tot is not None:
+            out["totals"] = tot
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.fpldpc_layered_destroy(self._h)
             self._h = None
 
 

@@ -16,6 +16,7 @@
 #include <sstream>
 
 #include "fpldpc_internal.hpp"
+#include "fpldpc_layered.hpp"
 
 namespace fpldpc {
 
@@ -247,6 +248,39 @@ static void fill_vlist(fpldpc_code *c) {
         }
 }
 
+// Layers of the layered decoder (fpldpc_layered.hpp): checks [l*L, (l+1)*L) may be updated at once
+// when no variable occurs twice among them.
+static bool layers_disjoint(const fpldpc_code &c, int L) {
+    std::vector<int> seen(c.n, -1);
+    for (int r = 0; r < c.m; r++)
+        for (int k = 0; k < c.cdeg[r]; k++) {
+            int &s = seen[c.clist[(size_t)r * c.dc_max + k]];
+            if (s == r / L) return false;
+            s = r / L;
+        }
+    return true;
+}
+
+int code_layering(const fpldpc_code &c, int layer_checks, int *L, int *layers) {
+    if (layer_checks < 0) return fail(FPLDPC_ERR_ARG, "layer_checks must be >= 0");
+    int use = layer_checks;
+    if (use == 0) {
+        use = 1;  // one check per layer is always valid: clist rows are strictly ascending
+        for (int cand : {c.array_p, c.qc_z})
+            if (cand > 1 && c.m % cand == 0 && layers_disjoint(c, cand)) {
+                use = cand;
+                break;
+            }
+    } else {
+        if (c.m % use) return fail(FPLDPC_ERR_ARG, "layer_checks does not divide the number of checks");
+        if (!layers_disjoint(c, use))
+            return fail(FPLDPC_ERR_UNSUPPORTED, "a variable occurs twice inside a layer of " + std::to_string(use) + " checks");
+    }
+    *L = use;
+    *layers = c.m / use;
+    return FPLDPC_OK;
+}
+
 }  // namespace fpldpc
 
 using namespace fpldpc;
@@ -399,6 +433,16 @@ int fpldpc_code_syndrome_host(fpldpc_code_t c, const uint8_t *bits) {
         if (x) return 1;
     }
     return 0;
+}
+
+int fpldpc_code_layering(fpldpc_code_t c, int32_t layer_checks, int32_t out[2]) {
+    if (!c || !out) return fail(FPLDPC_ERR_ARG, "null argument");
+    int L = 0, layers = 0;
+    const int st = code_layering(*c, layer_checks, &L, &layers);
+    if (st) return st;
+    out[0] = L;
+    out[1] = layers;
+    return FPLDPC_OK;
 }
 
 void fpldpc_code_free(fpldpc_code_t c) { delete c; }

@@ -1,0 +1,353 @@
+// fpldpc_layered.hip -- gfx950 (CDNA4) layered (row-serial) schedule of the fixed-point decoder.
+//
+// No reference counterpart: tyc85/FixedPointLDPC decodes by flooding only.  The arithmetic is the
+// reference's -- the box-plus FP_Decoder::sxor (ArrayLDPC_Decoder.cpp:677-694) and the serial
+// forward/backward fold of a check (:66-118) -- under the schedule fixed-point LDPC hardware uses
+// (DESIGN.md "Layered schedule"): per frame post[v] = LLR[v] and c2v[c][k] = 0; then, for every
+// iteration and for the checks c = 0 .. m-1 in code order, one after another,
+//     t[k] = post[v_k] - c2v[c][k];  new = fold(t);  c2v[c][k] = new[k];  post[v_k] = t[k] + new[k]
+// and after the last check hard[v] = post[v] > 0 ? 0 : 1 and the syndrome over clist.  Nothing is
+// saturated: results are defined while every intermediate fits int32 (the reference's arithmetic has
+// the same limit; unsaturated posteriors roughly double per layer once a frame is converging).
+//
+// Layers are parallelism, not semantics: checks [l*L, (l+1)*L) share no variable (validated at
+// creation, fpldpc_code_layering), so updating them at once gives what the serial order gives.
+//
+// Kernel (layered_generic): persistent grid, one workgroup per frame at a time, frames pulled from a
+// device work counter that the last workgroup out resets.  Posteriors are int32 in LDS.  Lane j takes
+// check l*L + j of the current layer (looping when L exceeds the workgroup); one __syncthreads()
+// separates layers.  A check's c2v entries are only ever touched by the lane that owns the check, so
+// the c2v state needs no synchronisation of its own: it lives in LDS (slot-major [dc_max][m], lanes
+// on consecutive words) when it fits the CU's 160 KiB beside the posteriors,
+// else in a per-workgroup global scratch; the index table joins it in LDS where that costs no resident
+// workgroup, and is read from global memory otherwise.  Forward array codes compute v = k*p + (j + i*k) mod p
+// instead of reading a table.  Hard decision, syndrome and error counts run once per iteration.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <utility>
+
+#include "fpldpc_layered.hpp"
+
+namespace fpldpc {
+namespace {
+
+constexpr int kLayMaxNT = 256;  // largest workgroup (4 waves); a decoder uses min(256, L rounded up to 64)
+constexpr int kLayMisc = 4;     // per-workgroup control words after the posteriors: [0] frame, [1] bit errors
+constexpr size_t kLdsMax = 160 * 1024;
+
+// x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
+// fpldpc_kernels.hip: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
+__device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
+    const int a = x < 0 ? -x : x;
+    const int b = y < 0 ? -y : y;
+    const int s = ((a + b) & mask) >> 2;
+    const int d = ((a > b ? a - b : b - a) & mask) >> 2;
+    const int p1 = max(C - s, 0);
+    const int p2 = max(C - d, 0);
+    const int r = min(a, b) + p1 - p2;
+    return ((x > 0) == (y > 0)) ? r : -r;
+}
+
+__device__ __forceinline__ int lay_load_llr(const LayeredArgs &a, size_t i) {
+    return a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];
+}
+
+// 1 if some check is unsatisfied by hard[v] = post[v] > 0 ? 0 : 1 (workgroup-uniform; a barrier).
+// cdeg: the degree table (LDS), unused when every check has degree DC (EXACT).
+template <int DC, bool EXACT>
+__device__ __forceinline__ int lay_syndrome(const LayeredArgs &a, const uint16_t *vidx, const uint8_t *cdeg,
+                                            const int *post) {
+    const int m = a.m, p = a.array_p;
+    int fail = 0;
+    for (int c = threadIdx.x; c < m; c += blockDim.x) {
+        const int deg = EXACT ? DC : (int)cdeg[c];
+        int ci = 0, col = 0;
+        if (!vidx) {
+            ci = c / p;
+            col = c - ci * p;
+        }
+        int par = 0;
+        for (int k = 0; k < deg; ++k) {
+            const int v = vidx ? (int)vidx[(size_t)k * m + c] : k * p + col;
+            col += ci;
+            if (col >= p) col -= p;
+            par ^= post[v] <= 0;
+        }
+        fail |= par;
+    }
+    return __syncthreads_or(fail);
+}
+
+// Frame epilogue: posteriors, packed hard decisions, per-frame bit errors and totals
+// ({bit errors, frames with errors, frames, iteration sum}, added to).
+__device__ __forceinline__ void lay_store(const LayeredArgs &a, int cw, const int *post, bool write_post, int iters,
+                                          int ok, int *misc) {
+    const int n = a.n, NT = blockDim.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (a.post && write_post)
+        for (int v = tid; v < n; v += NT) a.post[(size_t)cw * n + v] = post[v];
+    if (a.hard) {
+        uint32_t *h = a.hard + (size_t)cw * a.hard_words;
+        for (int base = wave * 64; base < n; base += NT) {
+            const int v = base + lane;
+            const unsigned long long b = __ballot(v < n && post[v] <= 0);
+            if (lane == 0) {
+                const int w = base >> 5;
+                h[w] = (uint32_t)b;
+                if (w + 1 < a.hard_words) h[w + 1] = (uint32_t)(b >> 32);
+            }
+        }
+    }
+    int errors = 0;
+    if (a.k_info > 0) {
+        int e = 0;
+        for (int i = tid; i < a.k_info; i += NT) e += ((post[a.info_idx[i]] <= 0) ? 1 : 0) != a.info_bits[i];
+        if (e) atomicAdd(&misc[1], e);
+        __syncthreads();
+        errors = misc[1];
+    }
+    if (tid == 0) {
+        if (a.iters) a.iters[cw] = iters;
+        if (a.syn_ok) a.syn_ok[cw] = (uint8_t)ok;
+        if (a.bit_errors) a.bit_errors[cw] = errors;
+        if (a.totals) {
+            atomicAdd(&a.totals[0], (unsigned long long)errors);
+            atomicAdd(&a.totals[1], (unsigned long long)(errors > 0));
+            atomicAdd(&a.totals[2], 1ull);
+            atomicAdd(&a.totals[3], (unsigned long long)iters);
+        }
+    }
+}
+
+// LDS: post [n] | misc [kLayMisc] | (LDS_STATE) c2v [dc_max][m] int32 | (table_lds) vidx [dc_max][m] uint16
+//      | (!EXACT) cdeg [m] uint8
+// EXACT: every check has degree DC -- the slot loops are straight-line code (A and R: DC = 47, a
+// quarter of the instructions of the predicated form); otherwise DC is the next of 8 / 16 / 32 / 48 /
+// 64, the degrees are staged in LDS once per workgroup and the slots are predicated per lane.
+template <int DC, bool LDS_STATE, bool EXACT>
+__global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
+    extern __shared__ __attribute__((aligned(16))) int lay_smem[];
+    const int n = a.n, m = a.m, p = a.array_p;
+    const int tid = threadIdx.x, NT = blockDim.x;
+    int *const post = lay_smem;
+    int *const misc = lay_smem + n;
+    int32_t *const c2v = LDS_STATE ? lay_smem + n + kLayMisc : a.c2v_scratch + (size_t)blockIdx.x * a.dc_max * m;
+    const uint16_t *vidx = a.vidx;  // null: computed addressing (forward array code)
+    if constexpr (LDS_STATE) {
+        if (a.table_lds) {
+            uint16_t *const lv = reinterpret_cast<uint16_t *>(lay_smem + n + kLayMisc + a.dc_max * m);
+            for (int i = tid; i < a.dc_max * m; i += NT) lv[i] = a.vidx[i];
+            vidx = lv;
+        }
+    }
+    const uint8_t *cdeg = nullptr;
+    if constexpr (!EXACT) {
+        const size_t edges = (size_t)a.dc_max * m;
+        uint8_t *const ld = reinterpret_cast<uint8_t *>(lay_smem + n + kLayMisc) +
+                            (LDS_STATE ? edges * sizeof(int32_t) + (a.table_lds ? edges * sizeof(uint16_t) : 0) : 0);
+        for (int i = tid; i < m; i += NT) ld[i] = a.cdeg[i];
+        cdeg = ld;
+    }
+
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) {
+            const int wi = atomicAdd(&a.counters[0], 1);
+            misc[0] = wi < a.batch ? wi : -1;
+            misc[1] = 0;
+        }
+        __syncthreads();
+        const int cw = misc[0];
+        if (cw < 0) break;
+        for (int v = tid; v < n; v += NT) post[v] = lay_load_llr(a, (size_t)cw * n + v);
+        __syncthreads();
+        // decode_fixpoint's channel pre-check (ArrayLDPC_Decoder.cpp:443-450): 0 iterations, the
+        // channel decision, posteriors left untouched
+        if (a.precheck && !lay_syndrome<DC, EXACT>(a, vidx, cdeg, post)) {
+            lay_store(a, cw, post, false, 0, 1, misc);
+            continue;
+        }
+        int iters = 0, fail = 1;
+        for (int it = 1; it <= a.max_iter; ++it) {
+            for (int l = 0; l < a.layers; ++l) {
+                for (int j = tid; j < a.L; j += NT) {
+                    const int c = l * a.L + j;
+                    const int deg = EXACT ? DC : (int)cdeg[c];
+                    int ci = 0, col = 0;
+                    if (!vidx) {
+                        ci = c / p;
+                        col = c - ci * p;
+                    }
+                    int mv[DC], vi[DC];
+#pragma unroll
+                    for (int k = 0; k < DC; ++k) {
+                        vi[k] = 0;
+                        mv[k] = 0;
+                        if (k < deg) {
+                            vi[k] = vidx ? (int)vidx[(size_t)k * m + c] : k * p + col;
+                            col += ci;
+                            if (col >= p) col -= p;
+                            const int old = it > 1 ? c2v[(size_t)k * m + c] : 0;  // c2v = 0 before the first update
+                            mv[k] = post[vi[k]] - old;
+                        }
+                    }
+                    // forward / backward fold (ArrayLDPC_Decoder.cpp:83-116), the reference's order
+                    int B[DC];
+                    B[DC - 1] = mv[DC - 1];
+#pragma unroll
+                    for (int k = DC - 2; k >= 1; --k)
+                        B[k] = k < deg - 1 ? lay_boxplus(B[k + 1], mv[k], a.C, a.mask) : mv[k];
+                    int F = mv[0];
+#pragma unroll
+                    for (int k = 0; k < DC; ++k) {
+                        if (k >= deg) continue;
+                        const int bn = B[k + 1 < DC ? k + 1 : k];  // (unused in the last slot)
+                        const int o = k == 0 ? bn : k == deg - 1 ? F : lay_boxplus(F, bn, a.C, a.mask);
+                        if (k > 0) F = lay_boxplus(F, mv[k], a.C, a.mask);
+                        c2v[(size_t)k * m + c] = o;
+                        post[vi[k]] = mv[k] + o;
+                    }
+                }
+                __syncthreads();  // the next layer reads the posteriors this one wrote
+            }
+            fail = lay_syndrome<DC, EXACT>(a, vidx, cdeg, post);
+            iters = it;
+            if (a.early_term && !fail) break;
+        }
+        lay_store(a, cw, post, true, iters, !fail, misc);
+    }
+    // the last workgroup out resets the counter block for the next call (every workgroup has made
+    // its last work-counter access, a returning atomic, before counting itself out)
+    if (tid == 0 && atomicAdd(&a.counters[1], 1) == (int)gridDim.x - 1) {
+        a.counters[0] = 0;
+        a.counters[1] = 0;
+    }
+}
+
+using LayeredFn = void (*)(LayeredArgs);
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is per kernel function and device, not per decoder: only
+// ever raise it, so that a later decoder with a smaller code does not take away what an earlier one
+// launches with.  Called with the decoder's device current.
+hipError_t raise_dynamic_lds(const void *fn, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> set;
+    int dev = 0;
+    hipError_t d = hipGetDevice(&dev);
+    if (d != hipSuccess) return d;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &cur = set[{dev, fn}];
+    if (bytes <= cur) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) cur = bytes;
+    return e;
+}
+
+constexpr int kExactDc = 47;  // the straight-line instantiation: the p = 47 array codes (A, R)
+
+LayeredFn layered_fn(int dc, bool lds_state, bool exact) {
+    if (exact) return lds_state ? layered_generic<kExactDc, true, true> : layered_generic<kExactDc, false, true>;
+    switch (dc) {
+        case 8: return lds_state ? layered_generic<8, true, false> : layered_generic<8, false, false>;
+        case 16: return lds_state ? layered_generic<16, true, false> : layered_generic<16, false, false>;
+        case 32: return lds_state ? layered_generic<32, true, false> : layered_generic<32, false, false>;
+        case 48: return lds_state ? layered_generic<48, true, false> : layered_generic<48, false, false>;
+        case 64: return lds_state ? layered_generic<64, true, false> : layered_generic<64, false, false>;
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+// Envelope: check degrees 2..64; n <= 40956 (4 B per posterior plus the control words, and one byte
+// per check unless the kernel's DC is every check's degree, within the CU's 160 KiB of LDS); any valid layer size.
+int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out) {
+    for (int r = 0; r < code.m; r++)
+        if (code.cdeg[r] < 2) return fail(FPLDPC_ERR_UNSUPPORTED, "check of degree < 2 (reference behaviour undefined)");
+    int dc = 0;
+    for (int d : {8, 16, 32, 48, 64})
+        if (!dc && code.dc_max <= d) dc = d;
+    if (!dc) return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: check degree above 64");
+    if ((size_t)(code.n + kLayMisc) * sizeof(int) > kLdsMax)
+        return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: code length above 40956 (int32 posteriors in 160 KiB of LDS)");
+    LayeredChoice lc;
+    lc.exact = code.regular_checks && code.dc_max == kExactDc;
+    lc.dc = lc.exact ? kExactDc : dc;
+    lc.computed = code.array_forward && code.array_p > 0;
+    // posteriors and control words, plus one byte per check for the degree table
+    const size_t base = (size_t)(code.n + kLayMisc) * sizeof(int) + (lc.exact ? 0 : (size_t)code.m);
+    if (base > kLdsMax)
+        return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: posteriors and check degrees do not fit 160 KiB of LDS");
+    const size_t edges = (size_t)code.dc_max * code.m;
+    // The index table joins c2v in LDS only where that costs no resident workgroup: the kernel is
+    // bound by latency at one or two waves per SIMD, and the table's reads (consecutive lanes,
+    // consecutive entries, addresses known ahead) are the ones global memory serves well.  W: 2
+    // workgroups per CU with the table in LDS (55 KB each), 4 without (40 KB): 17.0 -> 9.2 ms per 8192
+    // frames at 30 iterations (profiles/r7/layered/).
+    // Diagnostics, read at creation (A/B runs, and tests of those paths on small codes):
+    // FPLDPC_LAYERED_C2V=global keeps c2v and the index table in global memory even where they fit
+    // LDS; FPLDPC_LAYERED_TABLE=global / lds places the index table regardless of the rule above.
+    const char *force = getenv("FPLDPC_LAYERED_C2V");
+    const char *table = getenv("FPLDPC_LAYERED_TABLE");
+    const bool force_global = force && !strcmp(force, "global");
+    const size_t c2v_bytes = edges * sizeof(int32_t), tab_bytes = lc.computed ? 0 : edges * sizeof(uint16_t);
+    lc.threads = std::min(kLayMaxNT, (L + 63) / 64 * 64);
+    lc.lds_state = base + c2v_bytes <= kLdsMax && !force_global;
+    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact);
+    // resident workgroups per CU with `lds` bytes of LDS (0 and `e` set on an error)
+    hipError_t e = hipSuccess;
+    auto resident = [&](size_t lds) {
+        int per_cu = 0;
+        if (e == hipSuccess && lds > 64 * 1024) e = raise_dynamic_lds((const void *)fn, lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, lc.threads, lds);
+        return e == hipSuccess ? per_cu : 0;
+    };
+    if (lc.lds_state && tab_bytes && base + c2v_bytes + tab_bytes <= kLdsMax) {
+        if (table && (!strcmp(table, "lds") || !strcmp(table, "global")))
+            lc.table_lds = !strcmp(table, "lds");
+        else
+            lc.table_lds = resident(base + c2v_bytes + tab_bytes) == resident(base + c2v_bytes);
+        if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
+    }
+    lc.lds_bytes = base + (lc.lds_state ? c2v_bytes + (lc.table_lds ? tab_bytes : 0) : 0);
+    int per_cu = resident(lc.lds_bytes);
+    if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
+    if (per_cu < 1) return fail(FPLDPC_ERR_UNSUPPORTED, "layered kernel cannot be resident (occupancy 0)");
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
+    // global c2v: at most 4 workgroups per CU, so that the scratch (R: 212 KB per workgroup) stays
+    // within the L2 / Infinity Cache
+    if (!lc.lds_state) per_cu = std::min(per_cu, 4);
+    lc.grid = per_cu * prop.multiProcessorCount;
+    lc.scratch_ints = lc.lds_state ? 0 : (size_t)lc.grid * edges;
+    snprintf(lc.name, sizeof lc.name, "layered_generic<DC=%d,c2v=%s,addr=%s,deg=%s>", lc.dc, lc.lds_state ? "lds" : "global",
+             lc.computed ? "computed" : lc.table_lds ? "table" : "gtable", lc.exact ? "exact" : "table");
+    *out = lc;
+    return FPLDPC_OK;
+}
+
+int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream) {
+    if (args.batch <= 0) return FPLDPC_OK;
+    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact);
+    if (!fn) return fail(FPLDPC_ERR_ARG, "layered decoder has no kernel");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fn, dim3(std::min(lc.grid, args.batch)), dim3(lc.threads), lc.lds_bytes, s, args);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        // a launch that fails leaves the counter block for the next call to find non-zero: re-zero it
+        (void)hipMemsetAsync(args.counters, 0, kLayeredCounterInts * sizeof(int32_t), s);
+        return fail_hip(e, "layered kernel launch");
+    }
+    return FPLDPC_OK;
+}
+
+}  // namespace fpldpc

@@ -1,0 +1,81 @@
+// fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
+// (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* C ABI) and fpldpc_layered.hip (kernels).
+//
+// The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
+// c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding
+// kernels were compiled against them.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "fpldpc_internal.hpp"
+
+namespace fpldpc {
+
+// Resolves layer_checks (0 = auto: the array code's p, else qc_z when it gives valid layers, else 1)
+// and validates it: L divides m and no variable occurs twice among checks [l*L, (l+1)*L).
+int code_layering(const fpldpc_code &code, int layer_checks, int *L, int *layers);
+
+// Kernel choice of a layered decoder, made once at creation.
+struct LayeredChoice {
+    int dc = 0;              // kernel DC: 8 / 16 / 32 / 48 / 64 >= dc_max, or the exact degree (47)
+    bool lds_state = false;  // c2v (and the index table) in LDS; else per-workgroup global scratch
+    bool computed = false;   // forward array code: v = k*p + (j + i*k) mod p, no index table
+    bool table_lds = false;  // the index table is staged in LDS (with lds_state, table codes)
+    bool exact = false;      // every check has degree dc: straight-line slot loops, no degree table
+    int threads = 64;
+    int grid = 0;            // resident workgroups (persistent)
+    size_t lds_bytes = 0;
+    size_t scratch_ints = 0; // global c2v: grid * dc_max * m
+    char name[96] = "";
+};
+
+// Counter block of a layered decoder (int32): [0] work counter, [1] workgroups out of the kernel.
+// Zeroed at creation; the last workgroup out resets it, so a decode call issues kernels only.
+constexpr int kLayeredCounterInts = 2;
+
+struct LayeredArgs {
+    const void *llr = nullptr;
+    int llr_i16 = 0;
+    int n = 0, m = 0, dc_max = 0, L = 0, layers = 0, array_p = 0, table_lds = 0;
+    int batch = 0, max_iter = 30, C = 10, mask = 0xff, early_term = 1, precheck = 0;
+    const uint16_t *vidx = nullptr;  // [dc_max][m] var of slot k of check c (code order); null when computed
+    const uint8_t *cdeg = nullptr;   // [m]
+    uint32_t *hard = nullptr;
+    int hard_words = 0;
+    int32_t *iters = nullptr;
+    uint8_t *syn_ok = nullptr;
+    int32_t *post = nullptr;
+    int32_t *bit_errors = nullptr;
+    unsigned long long *totals = nullptr;
+    const int32_t *info_idx = nullptr;
+    const uint8_t *info_bits = nullptr;
+    int k_info = 0;
+    int *counters = nullptr;         // kLayeredCounterInts
+    int32_t *c2v_scratch = nullptr;  // [grid][dc_max][m] when !lds_state
+};
+
+// Envelope and kernel choice for (code, L) on `device`; FPLDPC_ERR_UNSUPPORTED outside the envelope.
+int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out);
+int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
+
+}  // namespace fpldpc
+
+// Layered decoder object (fpldpc_layered_t).
+struct fpldpc_layered {
+    fpldpc_code code;
+    fpldpc_params params{};
+    int device = 0;
+    int L = 0, layers = 0;
+    fpldpc::LayeredChoice lc;
+    uint16_t *d_vidx = nullptr;
+    uint8_t *d_cdeg = nullptr;
+    int *d_counter = nullptr;
+    int32_t *d_scratch = nullptr;
+    int32_t *d_info_idx = nullptr;
+    uint8_t *d_info_bits = nullptr;
+    int k_info = 0;
+    hipStream_t stream = nullptr;  // fpldpc_layered_decode_host staging
+    void *d_stage = nullptr;
+    size_t stage_bytes = 0;
+};

@@ -57,7 +57,8 @@ const char *fpldpc_last_error(void);
 const char *fpldpc_version(void);
 /* Content hash (16 hex digits) of the device sources and compile flags this library was built
  * from (no reference counterpart): committed profiler counters are bound to it, so that counters
- * measured on one kernel build are never reported for another. */
+ * measured on one kernel build are never reported for another.  It covers the kernels with committed
+ * counters (flooding, float, generation), not the layered decoder's. */
 const char *fpldpc_kernel_build_id(void);
 
 /* ---------------------------------------------------------------- parity-check codes */
@@ -171,6 +172,47 @@ int fpldpc_decode_float(fpldpc_decoder_t dec, const double *llr, int32_t batch, 
 int fpldpc_decode_float_host(fpldpc_decoder_t dec, const double *llr, int32_t batch, uint32_t *hard,
                              int32_t *iters, uint8_t *syndrome_ok, double *post, int32_t *bit_errors,
                              int64_t *totals);
+
+/* ---------------------------------------------------------------- layered decoder */
+/* The layered (row-serial) schedule of the same fixed-point arithmetic (no reference counterpart: the
+ * reference decodes by flooding only; this is the schedule quasi-cyclic / array-code hardware uses).
+ * Per frame post[v] = LLR[v] and c2v[c][k] = 0 for slot k (clist order) of check c.  With
+ * params.precheck the channel syndrome is tested first, as in fpldpc_decode.  Then, for
+ * it = 1 .. max_iter and for each check c = 0 .. m-1 in code (alist) order, one after another:
+ *     t[k] = post[v_k] - c2v[c][k]                                  (k < deg)
+ *     new  = the reference's forward/backward sxor fold of t        (ArrayLDPC_Decoder.cpp:66-118)
+ *     c2v[c][k] = new[k],  post[v_k] = t[k] + new[k]
+ * and after the last check hard[v] = post[v] > 0 ? 0 : 1, the syndrome over clist, iters = it; with
+ * early_term the frame stops on a pass.  Nothing is saturated.
+ * Envelope: results are defined while every intermediate fits int32 (the reference's own arithmetic
+ * has the same limit).  Unsaturated posteriors roughly double per layer once a frame is converging:
+ * the array code p = 47, r = 24 at 8 dB reaches 1.1e8 inside its single iteration, so a second
+ * iteration (early_term = 0) would leave int32.  Check degrees 2..64, n <= 40956.
+ * Layers are parallelism only, not semantics: checks [l*L, (l+1)*L) form layer l and are updated at
+ * once, which equals the serial order because no variable occurs twice inside a layer. */
+typedef struct fpldpc_layered *fpldpc_layered_t;
+/* Host only, no GPU: out = {layer_checks used, layers}.  layer_checks = 0 picks the array code's p,
+ * else qc_z when it gives valid layers, else 1 (always valid: rows are ascending).  FPLDPC_ERR_ARG
+ * if layer_checks < 0 or does not divide m, FPLDPC_ERR_UNSUPPORTED if a variable repeats inside a
+ * layer. */
+int fpldpc_code_layering(fpldpc_code_t code, int32_t layer_checks, int32_t out[2]);
+/* All six fpldpc_params fields apply.  FPLDPC_ERR_HIP without a HIP device, FPLDPC_ERR_UNSUPPORTED
+ * (with a message) outside the envelope above. */
+int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, fpldpc_layered_t *out);
+int fpldpc_layered_destroy(fpldpc_layered_t dec);
+/* Kernel variant, L, layers, resident workgroups, threads, LDS bytes. */
+int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap);
+/* As fpldpc_set_reference. */
+int fpldpc_layered_set_reference(fpldpc_layered_t dec, const int32_t *info_index, const uint8_t *info_bits, int32_t k);
+/* Conventions and outputs as fpldpc_decode: device pointers, asynchronous on `stream`, any output may
+ * be NULL, I32 / I16 LLRs, totals ADDED to; one object per stream (its calls share one work counter). */
+int fpldpc_layered_decode(fpldpc_layered_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                          int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors, int64_t *totals,
+                          void *stream);
+/* Same on host buffers (synchronous; stages through device memory owned by the decoder). */
+int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                               int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors,
+                               int64_t *totals);
 
 /* ---------------------------------------------------------------- channel model */
 /* Lehmer state after `draws` calls of Random() from `seed` (rngs.cpp:52-69, a = 48271,

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Layered against flooding at equal SNR: one JSON line per (config, Eb/N0, schedule) and one ratio
+line per point.  bench.py stays the flagship measurement; this tool answers what the layered
+schedule costs and buys on the same frames.
+
+For A (4096 frames) and W (8192 frames), reference-harness frames from seed 123456789, int16 LLRs
+resident in HBM: the flooding Decoder and the LayeredDecoder at 0 dB / -2 dB (no frame converges:
+all 30 iterations) and at 4.5 dB / 2 dB (the waterfall, early termination).  Timing as bench.py:
+device events around each decode call with every output and the totals, after a warm-up; the two
+schedules alternate step by step inside one timed window, and the median step is reported.
+
+usage: tools/bench_layered.py [--config A W] [--steps 30] [--warmup 5] [--layer-checks 0]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SEED = 123456789
+CONFIGS = {
+    # name: (code, batch, rate of the harness, (Eb/N0 where nothing converges, waterfall Eb/N0))
+    "A": (lambda F: F.Code.array(47, 5), 4096, None, (0.0, 4.5)),
+    "W": (lambda F: F.Code.wifi_1944_r12(), 8192, 0.5, (-2.0, 2.0)),  # the WiFi harness hard-codes R = 0.5
+}
+
+
+def git_head(arg):
+    if arg:
+        return arg
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], check=True, capture_output=True,
+                              text=True).stdout.strip()
+    except (OSError, subprocess.CalledProcessError):
+        return "unknown"
+
+
+class Leg:
+    """One decoder with its own output buffers and totals."""
+
+    def __init__(self, torch, dec, code, batch, dev):
+        k = code.n - code.rank
+        dec.set_reference(np.arange(k, dtype=np.int32), np.zeros(k, np.uint8))  # the all-zero codeword
+        self.dec, self.k, self.batch = dec, k, batch
+        self.hard = torch.empty((batch, dec.hard_words), dtype=torch.int32, device=dev)
+        self.iters = torch.empty(batch, dtype=torch.int32, device=dev)
+        self.ok = torch.empty(batch, dtype=torch.uint8, device=dev)
+        self.bit_err = torch.empty(batch, dtype=torch.int32, device=dev)
+        self.totals = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.ms = []
+
+    def step(self, llr, F, stream):
+        self.dec.decode_ptrs(llr.data_ptr(), F.FPLDPC_LLR_I16, self.batch, self.hard.data_ptr(), self.iters.data_ptr(),
+                             self.ok.data_ptr(), 0, self.bit_err.data_ptr(), self.totals.data_ptr(), stream.cuda_stream)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", nargs="+", default=["A", "W"], choices=sorted(CONFIGS))
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--min-warmup-s", type=float, default=0.5)
+    ap.add_argument("--layer-checks", type=int, default=0)
+    ap.add_argument("--git-head", default=None, help="recorded as git_head where the tree is not a git checkout")
+    args = ap.parse_args()
+    assert args.steps >= 20, "at least 20 timed steps"
+
+    import torch
+
+    import fixedpointldpc_amd as F
+    if not torch.cuda.is_available():
+        sys.exit("bench_layered.py needs the GPU (there is no CPU path)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.current_stream(dev)
+    common = {"kernel_build_id": F.lib().fpldpc_kernel_build_id().decode(), "git_head": git_head(args.git_head),
+              "device": torch.cuda.get_device_name(dev), "steps": args.steps, "timing": "device events, median step"}
+    for cfg in args.config:
+        mk, batch, rate, points = CONFIGS[cfg]
+        code = mk(F)
+        for ebn0 in points:
+            snr, sigma = F.snr_sigma(ebn0, rate or code.rate)
+            llr = torch.from_numpy(F.channel_llr(SEED, 0, batch, code.n, snr, sigma, 4, None, np.int16, nthreads=16)).to(dev)
+            legs = {"flooding": Leg(torch, F.Decoder(code, max_iter=30), code, batch, dev),
+                    "layered": Leg(torch, F.LayeredDecoder(code, max_iter=30, layer_checks=args.layer_checks), code,
+                                   batch, dev)}
+            t_w, n_w = time.perf_counter(), 0
+            while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
+                for leg in legs.values():
+                    leg.step(llr, F, stream)
+                n_w += 1
+                torch.cuda.synchronize(dev)
+            for leg in legs.values():
+                leg.totals.zero_()
+            torch.cuda.synchronize(dev)
+            ev = []
+            for _ in range(args.steps):  # the two schedules alternate inside one window
+                for name, leg in legs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    leg.step(llr, F, stream)
+                    e1.record(stream)
+                    ev.append((name, e0, e1))
+            torch.cuda.synchronize(dev)
+            for name, e0, e1 in ev:
+                legs[name].ms.append(e0.elapsed_time(e1))
+            rows = {}
+            for name, leg in legs.items():
+                tot = leg.totals.cpu().numpy()
+                med = float(np.median(leg.ms))
+                decoded = int(leg.ok.sum().item())  # frames whose output satisfies H
+                rows[name] = {
+                    "config": cfg, "ebn0_db": ebn0, "schedule": name, "frames": batch, "max_iter": 30, "early_term": 1,
+                    "describe": leg.dec.describe(), "median_ms": round(med, 4), "min_ms": round(float(np.min(leg.ms)), 4),
+                    "max_ms": round(float(np.max(leg.ms)), 4), "info_mbps": round(leg.k * batch / med / 1e3, 1),
+                    "frames_per_s": round(batch / med * 1e3, 1), "decoded_frames": decoded,
+                    "decoded_frames_per_s": round(decoded / med * 1e3, 1), "mean_iters": round(float(tot[3]) / float(tot[2]), 3),
+                    "frame_errors": int(tot[1]) // args.steps, "bit_errors": int(tot[0]) // args.steps, **common}
+                assert int(tot[2]) == batch * args.steps
+                print(json.dumps(rows[name]), flush=True)
+            f, l = rows["flooding"], rows["layered"]
+            print(json.dumps({
+                "config": cfg, "ebn0_db": ebn0, "ratio": "layered / flooding",
+                "frames_per_s": round(l["frames_per_s"] / f["frames_per_s"], 4),
+                "decoded_frames_per_s": (round(l["decoded_frames_per_s"] / f["decoded_frames_per_s"], 4)
+                                         if f["decoded_frames"] else None),
+                "mean_iters": round(l["mean_iters"] / f["mean_iters"], 4),
+                "frame_errors": [l["frame_errors"], f["frame_errors"]], **common}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
