@@ -103,6 +103,7 @@ def lib():
         "fpldpc_decode_frame_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P]),
         "fpldpc_code_layering": (ctypes.c_int, [P, I32, P]),
         "fpldpc_layered_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, ctypes.POINTER(P)]),
+        "fpldpc_layered_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, ctypes.POINTER(P)]),
         "fpldpc_layered_destroy": (ctypes.c_int, [P]),
         "fpldpc_layered_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
         "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
@@ -150,7 +151,7 @@ EXPORTED = [
     "fpldpc_encoder_dims", "fpldpc_encoder_info_index", "fpldpc_unpack_info_bytes", "fpldpc_encoder_encode_host",
     "fpldpc_encoder_free", "fpldpc_encoder_encode", "fpldpc_channel_llr",
     "fpldpc_decode_float", "fpldpc_decode_float_host",
-    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_destroy", "fpldpc_layered_describe",
+    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_destroy", "fpldpc_layered_describe",
     "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
 ]
@@ -404,10 +405,12 @@ class Decoder:
 
 class LayeredDecoder:
     """fpldpc_layered_t: the layered (row-serial) schedule of the fixed-point decoder, batched on the
-    GPU.  layer_checks = 0 picks the layer size (Code.layering).  Same outputs as Decoder."""
+    GPU.  layer_checks = 0 picks the layer size (Code.layering).  Same outputs as Decoder.
+    post_bits / msg_bits (both 0: nothing saturated) give the saturated decoder of
+    fpldpc_layered_create_sat, which is defined for every input."""
 
     def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
-                 layer_checks=0):
+                 layer_checks=0, post_bits=0, msg_bits=0):
         p = Params()
         lib().fpldpc_params_default(ctypes.byref(p))
         p.max_iter, p.frac_bits, p.width_mask = max_iter, frac_bits, width_mask
@@ -415,7 +418,11 @@ class LayeredDecoder:
         self.code = code
         self.params = p
         h = ctypes.c_void_p()
-        _check(lib().fpldpc_layered_create(code._h, ctypes.byref(p), layer_checks, ctypes.byref(h)))
+        if post_bits == 0 and msg_bits == 0:
+            _check(lib().fpldpc_layered_create(code._h, ctypes.byref(p), layer_checks, ctypes.byref(h)))
+        else:
+            _check(lib().fpldpc_layered_create_sat(code._h, ctypes.byref(p), layer_checks, post_bits, msg_bits,
+                                                   ctypes.byref(h)))
         self._h = h
         self.hard_words = (code.n + 31) // 32
 

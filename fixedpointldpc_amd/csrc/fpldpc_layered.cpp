@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "fpldpc_layered.hpp"
@@ -49,11 +51,11 @@ void free_layered(fpldpc_layered *d) {
 // Constant = int((5.0/8.0) * (1 << FRAC_WIDTH)) (ArrayLDPCMacro.h:175)
 int constant_c(int frac_bits) { return (int)((5.0 / 8.0) * (1 << frac_bits)); }
 
-}  // namespace
+int sat_limit(int bits) { return (1 << (bits - 1)) - 1; }
 
-extern "C" {
-
-int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, fpldpc_layered_t *out) {
+// sat: fpldpc_layered_create_sat (post_bits / msg_bits are validated before anything touches HIP).
+int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, bool sat, int32_t post_bits,
+           int32_t msg_bits, fpldpc_layered_t *out) {
     if (!code || !out) return fail(FPLDPC_ERR_ARG, "null argument");
     fpldpc_params p;
     fpldpc_params_default(&p);
@@ -61,6 +63,17 @@ int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32
     if (p.max_iter < 1 || p.max_iter > 100000) return fail(FPLDPC_ERR_ARG, "max_iter out of range (1..100000)");
     if (p.frac_bits < 0 || p.frac_bits > 16) return fail(FPLDPC_ERR_ARG, "frac_bits out of range");
     if (p.width_mask <= 0) return fail(FPLDPC_ERR_ARG, "width_mask must be positive");
+    int mode = kLayUnsat;
+    if (sat) {
+        if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 24))
+            return fail(FPLDPC_ERR_ARG, "saturated layered decoder: need 2 <= msg_bits < post_bits <= 24");
+        // a posterior pinned at S_p minus its own message (at most S_m + C) must keep its sign
+        if (sat_limit(post_bits) <= sat_limit(msg_bits) + constant_c(p.frac_bits))
+            return fail(FPLDPC_ERR_ARG, "saturated layered decoder: need S_p > S_m + C (2^(post_bits-1) - 1 > 2^(msg_bits-1) - 1 + " +
+                                            std::to_string(constant_c(p.frac_bits)) + ")");
+        const char *state = getenv("FPLDPC_LAYERED_STATE");  // diagnostic: int32 state where int16 would be chosen
+        mode = post_bits <= 16 && !(state && !strcmp(state, "i32")) ? kLaySat16 : kLaySat32;
+    }
     int L = 0, layers = 0;
     int st = code_layering(*code, layer_checks, &L, &layers);
     if (st) return st;
@@ -79,7 +92,9 @@ int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32
     d->device = dev;
     d->L = L;
     d->layers = layers;
-    st = layered_choose(d->code, L, dev, &d->lc);
+    d->post_bits = sat ? post_bits : 0;
+    d->msg_bits = sat ? msg_bits : 0;
+    st = layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
     const fpldpc_code &c = d->code;
     std::vector<uint8_t> cdeg(c.m);
@@ -97,10 +112,23 @@ int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32
     }
     HIP_TRY(hipMalloc(&d->d_counter, kLayeredCounterInts * sizeof(int32_t)));  // zero between calls
     HIP_TRY(hipMemset(d->d_counter, 0, kLayeredCounterInts * sizeof(int32_t)));
-    if (d->lc.scratch_ints) HIP_TRY(hipMalloc(&d->d_scratch, d->lc.scratch_ints * sizeof(int32_t)));
+    if (d->lc.scratch_bytes) HIP_TRY(hipMalloc(&d->d_scratch, d->lc.scratch_bytes));
     HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     *out = d.release();
     return FPLDPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, fpldpc_layered_t *out) {
+    return create(code, params, layer_checks, false, 0, 0, out);
+}
+
+int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, int32_t post_bits,
+                              int32_t msg_bits, fpldpc_layered_t *out) {
+    return create(code, params, layer_checks, true, post_bits, msg_bits, out);
 }
 
 int fpldpc_layered_destroy(fpldpc_layered_t dec) {
@@ -110,8 +138,11 @@ int fpldpc_layered_destroy(fpldpc_layered_t dec) {
 
 int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
-    snprintf(buf, cap, "%s L=%d layers=%d grid=%d threads=%d lds=%zu device=%d", dec->lc.name, dec->L, dec->layers,
-             dec->lc.grid, dec->lc.threads, dec->lc.lds_bytes, dec->device);
+    const int w = snprintf(buf, cap, "%s L=%d layers=%d grid=%d threads=%d lds=%zu device=%d", dec->lc.name, dec->L,
+                           dec->layers, dec->lc.grid, dec->lc.threads, dec->lc.lds_bytes, dec->device);
+    if (dec->lc.mode != kLayUnsat && w > 0 && (size_t)w < cap)
+        snprintf(buf + w, cap - w, " sat=%d/%d state=%s", dec->post_bits, dec->msg_bits,
+                 dec->lc.mode == kLaySat16 ? "i16" : "i32");
     return FPLDPC_OK;
 }
 
@@ -179,6 +210,10 @@ int fpldpc_layered_decode(fpldpc_layered_t dec, const void *llr, int32_t llr_typ
     a.k_info = dec->k_info;
     a.counters = dec->d_counter;
     a.c2v_scratch = dec->d_scratch;
+    if (dec->lc.mode != kLayUnsat) {
+        a.sat_post = sat_limit(dec->post_bits);
+        a.sat_msg = sat_limit(dec->msg_bits);
+    }
     return layered_launch(dec->lc, a, stream);
 }
 

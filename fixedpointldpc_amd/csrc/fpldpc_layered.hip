@@ -22,6 +22,14 @@
 // else in a per-workgroup global scratch; the index table joins it in LDS where that costs no resident
 // workgroup, and is read from global memory otherwise.  Forward array codes compute v = k*p + (j + i*k) mod p
 // instead of reading a table.  Hard decision, syndrome and error counts run once per iteration.
+//
+// Saturated form (fpldpc_layered_create_sat, include/fpldpc.h): the same kernel with
+//     post[v] = clamp(LLR[v], S_p);  t[k] = clamp(post[v_k] - c2v[c][k], S_m);  post[v_k] = clamp(t[k] + new[k], S_p)
+// which bounds every c2v by S_m + C and every posterior by S_p, for every input.  With post_bits <= 16
+// the on-chip state (posteriors and c2v) is int16 -- half the LDS per frame, and R's c2v fits LDS --
+// with the arithmetic in int32 registers; lanes of a layer write distinct posteriors with native
+// 16-bit LDS stores, so two lanes on the halves of one word never read-modify-write it.  With
+// post_bits 17..24 the state stays int32.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +51,17 @@ constexpr int kLayMaxNT = 256;  // largest workgroup (4 waves); a decoder uses m
 constexpr int kLayMisc = 4;     // per-workgroup control words after the posteriors: [0] frame, [1] bit errors
 constexpr size_t kLdsMax = 160 * 1024;
 
+// State of a kernel instantiation (MODE): the type of the posteriors and c2v; the clamps run in the two
+// saturated modes.
+template <int MODE> struct LayState { using type = int32_t; };
+template <> struct LayState<kLaySat16> { using type = int16_t; };
+
+constexpr size_t lay_state_bytes(int mode) { return mode == kLaySat16 ? sizeof(int16_t) : sizeof(int32_t); }
+// 32-bit words that n posteriors take in front of the control words
+__host__ __device__ constexpr size_t lay_post_words(int mode, int n) { return ((size_t)n * lay_state_bytes(mode) + 3) / 4; }
+
+__device__ __forceinline__ int lay_clamp(int x, int S) { return min(max(x, -S), S); }
+
 // x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
 // fpldpc_kernels.hip: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
 __device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
@@ -62,9 +81,9 @@ __device__ __forceinline__ int lay_load_llr(const LayeredArgs &a, size_t i) {
 
 // 1 if some check is unsatisfied by hard[v] = post[v] > 0 ? 0 : 1 (workgroup-uniform; a barrier).
 // cdeg: the degree table (LDS), unused when every check has degree DC (EXACT).
-template <int DC, bool EXACT>
+template <int DC, bool EXACT, typename ST>
 __device__ __forceinline__ int lay_syndrome(const LayeredArgs &a, const uint16_t *vidx, const uint8_t *cdeg,
-                                            const int *post) {
+                                            const ST *post) {
     const int m = a.m, p = a.array_p;
     int fail = 0;
     for (int c = threadIdx.x; c < m; c += blockDim.x) {
@@ -88,7 +107,8 @@ __device__ __forceinline__ int lay_syndrome(const LayeredArgs &a, const uint16_t
 
 // Frame epilogue: posteriors, packed hard decisions, per-frame bit errors and totals
 // ({bit errors, frames with errors, frames, iteration sum}, added to).
-__device__ __forceinline__ void lay_store(const LayeredArgs &a, int cw, const int *post, bool write_post, int iters,
+template <typename ST>
+__device__ __forceinline__ void lay_store(const LayeredArgs &a, int cw, const ST *post, bool write_post, int iters,
                                           int ok, int *misc) {
     const int n = a.n, NT = blockDim.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -127,23 +147,27 @@ __device__ __forceinline__ void lay_store(const LayeredArgs &a, int cw, const in
     }
 }
 
-// LDS: post [n] | misc [kLayMisc] | (LDS_STATE) c2v [dc_max][m] int32 | (table_lds) vidx [dc_max][m] uint16
-//      | (!EXACT) cdeg [m] uint8
+// LDS: post [n] ST (up to a whole word) | misc [kLayMisc] | (LDS_STATE) c2v [dc_max][m] ST
+//      | (table_lds) vidx [dc_max][m] uint16 | (!EXACT) cdeg [m] uint8;  ST = int16 in MODE kLaySat16, else int32
 // EXACT: every check has degree DC -- the slot loops are straight-line code (A and R: DC = 47, a
 // quarter of the instructions of the predicated form); otherwise DC is the next of 8 / 16 / 32 / 48 /
 // 64, the degrees are staged in LDS once per workgroup and the slots are predicated per lane.
-template <int DC, bool LDS_STATE, bool EXACT>
+// MODE: kLayUnsat (nothing saturated, int32 state), kLaySat32 / kLaySat16 (the clamps at a.sat_post / a.sat_msg).
+template <int DC, bool LDS_STATE, bool EXACT, int MODE>
 __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
+    using ST = typename LayState<MODE>::type;
+    constexpr bool SAT = MODE != kLayUnsat;
     extern __shared__ __attribute__((aligned(16))) int lay_smem[];
     const int n = a.n, m = a.m, p = a.array_p;
     const int tid = threadIdx.x, NT = blockDim.x;
-    int *const post = lay_smem;
-    int *const misc = lay_smem + n;
-    int32_t *const c2v = LDS_STATE ? lay_smem + n + kLayMisc : a.c2v_scratch + (size_t)blockIdx.x * a.dc_max * m;
+    ST *const post = reinterpret_cast<ST *>(lay_smem);
+    int *const misc = lay_smem + lay_post_words(MODE, n);
+    ST *const c2v = LDS_STATE ? reinterpret_cast<ST *>(misc + kLayMisc)
+                              : static_cast<ST *>(a.c2v_scratch) + (size_t)blockIdx.x * a.dc_max * m;
     const uint16_t *vidx = a.vidx;  // null: computed addressing (forward array code)
     if constexpr (LDS_STATE) {
         if (a.table_lds) {
-            uint16_t *const lv = reinterpret_cast<uint16_t *>(lay_smem + n + kLayMisc + a.dc_max * m);
+            uint16_t *const lv = reinterpret_cast<uint16_t *>(c2v + a.dc_max * m);
             for (int i = tid; i < a.dc_max * m; i += NT) lv[i] = a.vidx[i];
             vidx = lv;
         }
@@ -151,8 +175,8 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
     const uint8_t *cdeg = nullptr;
     if constexpr (!EXACT) {
         const size_t edges = (size_t)a.dc_max * m;
-        uint8_t *const ld = reinterpret_cast<uint8_t *>(lay_smem + n + kLayMisc) +
-                            (LDS_STATE ? edges * sizeof(int32_t) + (a.table_lds ? edges * sizeof(uint16_t) : 0) : 0);
+        uint8_t *const ld = reinterpret_cast<uint8_t *>(misc + kLayMisc) +
+                            (LDS_STATE ? edges * sizeof(ST) + (a.table_lds ? edges * sizeof(uint16_t) : 0) : 0);
         for (int i = tid; i < m; i += NT) ld[i] = a.cdeg[i];
         cdeg = ld;
     }
@@ -167,7 +191,11 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
         __syncthreads();
         const int cw = misc[0];
         if (cw < 0) break;
-        for (int v = tid; v < n; v += NT) post[v] = lay_load_llr(a, (size_t)cw * n + v);
+        for (int v = tid; v < n; v += NT) {
+            int x = lay_load_llr(a, (size_t)cw * n + v);
+            if constexpr (SAT) x = lay_clamp(x, a.sat_post);  // (sign and zero are kept: S_p >= 1)
+            post[v] = (ST)x;
+        }
         __syncthreads();
         // decode_fixpoint's channel pre-check (ArrayLDPC_Decoder.cpp:443-450): 0 iterations, the
         // channel decision, posteriors left untouched
@@ -195,8 +223,9 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
                             vi[k] = vidx ? (int)vidx[(size_t)k * m + c] : k * p + col;
                             col += ci;
                             if (col >= p) col -= p;
-                            const int old = it > 1 ? c2v[(size_t)k * m + c] : 0;  // c2v = 0 before the first update
-                            mv[k] = post[vi[k]] - old;
+                            const int old = it > 1 ? (int)c2v[(size_t)k * m + c] : 0;  // c2v = 0 before the first update
+                            mv[k] = (int)post[vi[k]] - old;
+                            if constexpr (SAT) mv[k] = lay_clamp(mv[k], a.sat_msg);
                         }
                     }
                     // forward / backward fold (ArrayLDPC_Decoder.cpp:83-116), the reference's order
@@ -212,8 +241,10 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
                         const int bn = B[k + 1 < DC ? k + 1 : k];  // (unused in the last slot)
                         const int o = k == 0 ? bn : k == deg - 1 ? F : lay_boxplus(F, bn, a.C, a.mask);
                         if (k > 0) F = lay_boxplus(F, mv[k], a.C, a.mask);
-                        c2v[(size_t)k * m + c] = o;
-                        post[vi[k]] = mv[k] + o;
+                        c2v[(size_t)k * m + c] = (ST)o;  // |o| <= S_m + C: inside int16 where the state is
+                        int q = mv[k] + o;
+                        if constexpr (SAT) q = lay_clamp(q, a.sat_post);
+                        post[vi[k]] = (ST)q;
                     }
                 }
                 __syncthreads();  // the next layer reads the posteriors this one wrote
@@ -253,37 +284,51 @@ hipError_t raise_dynamic_lds(const void *fn, size_t bytes) {
 
 constexpr int kExactDc = 47;  // the straight-line instantiation: the p = 47 array codes (A, R)
 
-LayeredFn layered_fn(int dc, bool lds_state, bool exact) {
-    if (exact) return lds_state ? layered_generic<kExactDc, true, true> : layered_generic<kExactDc, false, true>;
+template <int MODE>
+LayeredFn layered_fn_of(int dc, bool lds_state, bool exact) {
+    if (exact) return lds_state ? layered_generic<kExactDc, true, true, MODE> : layered_generic<kExactDc, false, true, MODE>;
     switch (dc) {
-        case 8: return lds_state ? layered_generic<8, true, false> : layered_generic<8, false, false>;
-        case 16: return lds_state ? layered_generic<16, true, false> : layered_generic<16, false, false>;
-        case 32: return lds_state ? layered_generic<32, true, false> : layered_generic<32, false, false>;
-        case 48: return lds_state ? layered_generic<48, true, false> : layered_generic<48, false, false>;
-        case 64: return lds_state ? layered_generic<64, true, false> : layered_generic<64, false, false>;
+        case 8: return lds_state ? layered_generic<8, true, false, MODE> : layered_generic<8, false, false, MODE>;
+        case 16: return lds_state ? layered_generic<16, true, false, MODE> : layered_generic<16, false, false, MODE>;
+        case 32: return lds_state ? layered_generic<32, true, false, MODE> : layered_generic<32, false, false, MODE>;
+        case 48: return lds_state ? layered_generic<48, true, false, MODE> : layered_generic<48, false, false, MODE>;
+        case 64: return lds_state ? layered_generic<64, true, false, MODE> : layered_generic<64, false, false, MODE>;
+    }
+    return nullptr;
+}
+
+LayeredFn layered_fn(int dc, bool lds_state, bool exact, int mode) {
+    switch (mode) {
+        case kLayUnsat: return layered_fn_of<kLayUnsat>(dc, lds_state, exact);
+        case kLaySat32: return layered_fn_of<kLaySat32>(dc, lds_state, exact);
+        case kLaySat16: return layered_fn_of<kLaySat16>(dc, lds_state, exact);
     }
     return nullptr;
 }
 
 }  // namespace
 
-// Envelope: check degrees 2..64; n <= 40956 (4 B per posterior plus the control words, and one byte
-// per check unless the kernel's DC is every check's degree, within the CU's 160 KiB of LDS); any valid layer size.
-int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out) {
+// Envelope: check degrees 2..64; any valid layer size; the posteriors (4 B each, 2 B with int16 state),
+// the control words and one byte per check (unless the kernel's DC is every check's degree) within the
+// CU's 160 KiB of LDS: n <= 40956 with int32 state; with int16 state every code object's n (<= 65535:
+// 128 KiB of posteriors) as long as its degree table fits beside them.
+int layered_choose(const fpldpc_code &code, int L, int device, int mode, LayeredChoice *out) {
     for (int r = 0; r < code.m; r++)
         if (code.cdeg[r] < 2) return fail(FPLDPC_ERR_UNSUPPORTED, "check of degree < 2 (reference behaviour undefined)");
     int dc = 0;
     for (int d : {8, 16, 32, 48, 64})
         if (!dc && code.dc_max <= d) dc = d;
     if (!dc) return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: check degree above 64");
-    if ((size_t)(code.n + kLayMisc) * sizeof(int) > kLdsMax)
+    const size_t state = lay_state_bytes(mode);
+    if (mode != kLaySat16 && (size_t)(code.n + kLayMisc) * sizeof(int) > kLdsMax)
         return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: code length above 40956 (int32 posteriors in 160 KiB of LDS)");
     LayeredChoice lc;
+    lc.mode = mode;
     lc.exact = code.regular_checks && code.dc_max == kExactDc;
     lc.dc = lc.exact ? kExactDc : dc;
     lc.computed = code.array_forward && code.array_p > 0;
     // posteriors and control words, plus one byte per check for the degree table
-    const size_t base = (size_t)(code.n + kLayMisc) * sizeof(int) + (lc.exact ? 0 : (size_t)code.m);
+    const size_t base = (lay_post_words(mode, code.n) + kLayMisc) * sizeof(int) + (lc.exact ? 0 : (size_t)code.m);
     if (base > kLdsMax)
         return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: posteriors and check degrees do not fit 160 KiB of LDS");
     const size_t edges = (size_t)code.dc_max * code.m;
@@ -294,14 +339,15 @@ int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *ou
     // frames at 30 iterations (profiles/r7/layered/).
     // Diagnostics, read at creation (A/B runs, and tests of those paths on small codes):
     // FPLDPC_LAYERED_C2V=global keeps c2v and the index table in global memory even where they fit
-    // LDS; FPLDPC_LAYERED_TABLE=global / lds places the index table regardless of the rule above.
+    // LDS, =lds keeps c2v in LDS wherever it fits; FPLDPC_LAYERED_TABLE=global / lds places the index
+    // table regardless of the rule above.
     const char *force = getenv("FPLDPC_LAYERED_C2V");
     const char *table = getenv("FPLDPC_LAYERED_TABLE");
-    const bool force_global = force && !strcmp(force, "global");
-    const size_t c2v_bytes = edges * sizeof(int32_t), tab_bytes = lc.computed ? 0 : edges * sizeof(uint16_t);
+    const bool force_global = force && !strcmp(force, "global"), force_lds = force && !strcmp(force, "lds");
+    const size_t c2v_bytes = edges * state, tab_bytes = lc.computed ? 0 : edges * sizeof(uint16_t);
     lc.threads = std::min(kLayMaxNT, (L + 63) / 64 * 64);
     lc.lds_state = base + c2v_bytes <= kLdsMax && !force_global;
-    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact);
+    LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact, mode);
     // resident workgroups per CU with `lds` bytes of LDS (0 and `e` set on an error)
     hipError_t e = hipSuccess;
     auto resident = [&](size_t lds) {
@@ -310,6 +356,18 @@ int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *ou
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, lc.threads, lds);
         return e == hipSuccess ? per_cu : 0;
     };
+    // Saturated decoders: a c2v that fits LDS but leaves one workgroup per CU resident (R with int16
+    // state: 110 KB) goes to the global scratch with its 4 workgroups per CU instead -- the kernel runs
+    // at the latency of its dependent chain, and one wave per CU hides none of it (measured
+    // on R).  The unsaturated decoder keeps its rule: LDS wherever c2v fits.
+    if (mode != kLayUnsat && lc.lds_state && !force_lds) {
+        const int with_lds = resident(base + c2v_bytes);
+        if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
+        if (with_lds < 2) {
+            lc.lds_state = false;
+            fn = layered_fn(lc.dc, false, lc.exact, mode);
+        }
+    }
     if (lc.lds_state && tab_bytes && base + c2v_bytes + tab_bytes <= kLdsMax) {
         if (table && (!strcmp(table, "lds") || !strcmp(table, "global")))
             lc.table_lds = !strcmp(table, "lds");
@@ -324,20 +382,21 @@ int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *ou
     hipDeviceProp_t prop;
     e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
-    // global c2v: at most 4 workgroups per CU, so that the scratch (R: 212 KB per workgroup) stays
-    // within the L2 / Infinity Cache
+    // global c2v: at most 4 workgroups per CU, so that the scratch (R: 212 KB per workgroup, 106 KB with
+    // int16 state) stays within the L2 / Infinity Cache
     if (!lc.lds_state) per_cu = std::min(per_cu, 4);
     lc.grid = per_cu * prop.multiProcessorCount;
-    lc.scratch_ints = lc.lds_state ? 0 : (size_t)lc.grid * edges;
-    snprintf(lc.name, sizeof lc.name, "layered_generic<DC=%d,c2v=%s,addr=%s,deg=%s>", lc.dc, lc.lds_state ? "lds" : "global",
-             lc.computed ? "computed" : lc.table_lds ? "table" : "gtable", lc.exact ? "exact" : "table");
+    lc.scratch_bytes = lc.lds_state ? 0 : (size_t)lc.grid * edges * state;
+    snprintf(lc.name, sizeof lc.name, "%s<DC=%d,c2v=%s,addr=%s,deg=%s>", mode == kLayUnsat ? "layered_generic" : "layered_sat",
+             lc.dc, lc.lds_state ? "lds" : "global", lc.computed ? "computed" : lc.table_lds ? "table" : "gtable",
+             lc.exact ? "exact" : "table");
     *out = lc;
     return FPLDPC_OK;
 }
 
 int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream) {
     if (args.batch <= 0) return FPLDPC_OK;
-    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact);
+    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact, lc.mode);
     if (!fn) return fail(FPLDPC_ERR_ARG, "layered decoder has no kernel");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(fn, dim3(std::min(lc.grid, args.batch)), dim3(lc.threads), lc.lds_bytes, s, args);

@@ -16,8 +16,13 @@ namespace fpldpc {
 // and validates it: L divides m and no variable occurs twice among checks [l*L, (l+1)*L).
 int code_layering(const fpldpc_code &code, int layer_checks, int *L, int *layers);
 
+// State of a layered decoder: nothing saturated (fpldpc_layered_create: int32 posteriors and c2v), or
+// the clamps of fpldpc_layered_create_sat with int32 state (post_bits 17..24) or int16 state (<= 16).
+enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2 };
+
 // Kernel choice of a layered decoder, made once at creation.
 struct LayeredChoice {
+    int mode = kLayUnsat;
     int dc = 0;              // kernel DC: 8 / 16 / 32 / 48 / 64 >= dc_max, or the exact degree (47)
     bool lds_state = false;  // c2v (and the index table) in LDS; else per-workgroup global scratch
     bool computed = false;   // forward array code: v = k*p + (j + i*k) mod p, no index table
@@ -26,7 +31,7 @@ struct LayeredChoice {
     int threads = 64;
     int grid = 0;            // resident workgroups (persistent)
     size_t lds_bytes = 0;
-    size_t scratch_ints = 0; // global c2v: grid * dc_max * m
+    size_t scratch_bytes = 0; // global c2v: grid * dc_max * m entries of the state type
     char name[96] = "";
 };
 
@@ -43,6 +48,8 @@ struct LayeredArgs {
     const uint8_t *cdeg = nullptr;   // [m]
     uint32_t *hard = nullptr;
     int hard_words = 0;
+    int sat_post = 0;                // S_p of a saturated decoder (this and sat_msg sit in what was padding:
+                                     // the unsaturated kernels keep their argument layout)
     int32_t *iters = nullptr;
     uint8_t *syn_ok = nullptr;
     int32_t *post = nullptr;
@@ -51,12 +58,13 @@ struct LayeredArgs {
     const int32_t *info_idx = nullptr;
     const uint8_t *info_bits = nullptr;
     int k_info = 0;
+    int sat_msg = 0;                 // S_m
     int *counters = nullptr;         // kLayeredCounterInts
-    int32_t *c2v_scratch = nullptr;  // [grid][dc_max][m] when !lds_state
+    void *c2v_scratch = nullptr;     // [grid][dc_max][m] of the state type when !lds_state
 };
 
-// Envelope and kernel choice for (code, L) on `device`; FPLDPC_ERR_UNSUPPORTED outside the envelope.
-int layered_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out);
+// Envelope and kernel choice for (code, L, mode) on `device`; FPLDPC_ERR_UNSUPPORTED outside the envelope.
+int layered_choose(const fpldpc_code &code, int L, int device, int mode, LayeredChoice *out);
 int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
 
 }  // namespace fpldpc
@@ -67,11 +75,12 @@ struct fpldpc_layered {
     fpldpc_params params{};
     int device = 0;
     int L = 0, layers = 0;
+    int post_bits = 0, msg_bits = 0;  // fpldpc_layered_create_sat; 0: unsaturated
     fpldpc::LayeredChoice lc;
     uint16_t *d_vidx = nullptr;
     uint8_t *d_cdeg = nullptr;
     int *d_counter = nullptr;
-    int32_t *d_scratch = nullptr;
+    void *d_scratch = nullptr;
     int32_t *d_info_idx = nullptr;
     uint8_t *d_info_bits = nullptr;
     int k_info = 0;

@@ -183,7 +183,8 @@ int fpldpc_decode_float_host(fpldpc_decoder_t dec, const double *llr, int32_t ba
  *     new  = the reference's forward/backward sxor fold of t        (ArrayLDPC_Decoder.cpp:66-118)
  *     c2v[c][k] = new[k],  post[v_k] = t[k] + new[k]
  * and after the last check hard[v] = post[v] > 0 ? 0 : 1, the syndrome over clist, iters = it; with
- * early_term the frame stops on a pass.  Nothing is saturated.
+ * early_term the frame stops on a pass.  Nothing is saturated (fpldpc_layered_create_sat is the
+ * saturated form, defined for every input).
  * Envelope: results are defined while every intermediate fits int32 (the reference's own arithmetic
  * has the same limit).  Unsaturated posteriors roughly double per layer once a frame is converging:
  * the array code p = 47, r = 24 at 8 dB reaches 1.1e8 inside its single iteration, so a second
@@ -199,6 +200,32 @@ int fpldpc_code_layering(fpldpc_code_t code, int32_t layer_checks, int32_t out[2
 /* All six fpldpc_params fields apply.  FPLDPC_ERR_HIP without a HIP device, FPLDPC_ERR_UNSUPPORTED
  * (with a message) outside the envelope above. */
 int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, fpldpc_layered_t *out);
+/* The saturated layered decoder: the same schedule with posteriors post_bits wide and messages msg_bits
+ * wide, defined for EVERY input (the unsaturated one above only while its intermediates fit int32).
+ * With S_p = 2^(post_bits-1) - 1, S_m = 2^(msg_bits-1) - 1, clamp(x, S) = min(max(x, -S), S) and
+ * C = the reference's Constant, int(5/8 * 2^frac_bits), per frame
+ *     post[v] = clamp(LLR[v], S_p);  c2v[c][k] = 0
+ *     for it = 1 .. max_iter, for each check c in code order:
+ *         t[k]      = clamp(post[v_k] - c2v[c][k], S_m)
+ *         new       = the reference's forward/backward sxor fold of t      (unchanged)
+ *         c2v[c][k] = new[k]
+ *         post[v_k] = clamp(t[k] + new[k], S_p)
+ * Hard decision, syndrome, iters, early termination, layers and outputs as above (post stays int32);
+ * precheck tests the clamped LLRs (the clamp keeps every sign) and leaves post untouched.
+ * Bounds: |sxor(x, y)| <= min(|x|, |y|) + C, so every fold value and every c2v is at most S_m + C,
+ * |post| <= S_p, and in registers |post - c2v| <= S_p + S_m + C and |t + new| <= 2 S_m + C.
+ * FPLDPC_ERR_ARG (with a message, tested before a HIP device is looked for) unless
+ *     2 <= msg_bits < post_bits <= 24   and   S_p > S_m + C.
+ * Two widths, because one does not work: sgn(0) = -1 in the reference's sxor, and with S_m = S_p a
+ * posterior pinned at S_p minus its own message near S_p gives t = 0, a message of the wrong sign (A at
+ * 8 dB: no frame decodes).  S_p > S_m + C is that reason as a rule: a pinned posterior minus its own
+ * message (at most S_m + C) keeps its sign.
+ * post_bits <= 16 keeps posteriors and c2v as int16 on chip (S_m + C <= 32767 follows from the rule),
+ * 17..24 as int32.  Check degrees 2..64; n <= 40956 with int32 state, any code's n (<= 65535) with int16 state.
+ * The object is an fpldpc_layered_t like any other: destroy, describe (which adds sat=<post_bits>/<msg_bits>
+ * and state=i16|i32), set_reference, decode and decode_host below apply unchanged. */
+int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks,
+                              int32_t post_bits, int32_t msg_bits, fpldpc_layered_t *out);
 int fpldpc_layered_destroy(fpldpc_layered_t dec);
 /* Kernel variant, L, layers, resident workgroups, threads, LDS bytes. */
 int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap);

@@ -9,7 +9,13 @@ all 30 iterations) and at 4.5 dB / 2 dB (the waterfall, early termination).  Tim
 device events around each decode call with every output and the totals, after a warm-up; the two
 schedules alternate step by step inside one timed window, and the median step is reported.
 
+--post-bits / --msg-bits add a third decoder to the same window: the saturated layered decoder
+(fpldpc_layered_create_sat) at those widths.  R (4096 frames, 6.5 dB) is measured on request
+(--config R): its unsaturated layered line is only as good as int32 holds at that SNR.  The
+FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
+
 usage: tools/bench_layered.py [--config A W] [--steps 30] [--warmup 5] [--layer-checks 0]
+                              [--post-bits 12 --msg-bits 10]
 """
 import argparse
 import json
@@ -27,6 +33,7 @@ CONFIGS = {
     # name: (code, batch, rate of the harness, (Eb/N0 where nothing converges, waterfall Eb/N0))
     "A": (lambda F: F.Code.array(47, 5), 4096, None, (0.0, 4.5)),
     "W": (lambda F: F.Code.wifi_1944_r12(), 8192, 0.5, (-2.0, 2.0)),  # the WiFi harness hard-codes R = 0.5
+    "R": (lambda F: F.Code.array(47, 24), 4096, None, (6.5,)),
 }
 
 
@@ -66,6 +73,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--min-warmup-s", type=float, default=0.5)
     ap.add_argument("--layer-checks", type=int, default=0)
+    ap.add_argument("--post-bits", type=int, default=0, help="with --msg-bits: also time the saturated layered decoder")
+    ap.add_argument("--msg-bits", type=int, default=0)
     ap.add_argument("--git-head", default=None, help="recorded as git_head where the tree is not a git checkout")
     args = ap.parse_args()
     assert args.steps >= 20, "at least 20 timed steps"
@@ -89,6 +98,10 @@ def main():
             legs = {"flooding": Leg(torch, F.Decoder(code, max_iter=30), code, batch, dev),
                     "layered": Leg(torch, F.LayeredDecoder(code, max_iter=30, layer_checks=args.layer_checks), code,
                                    batch, dev)}
+            if args.post_bits or args.msg_bits:
+                legs["layered_sat"] = Leg(torch, F.LayeredDecoder(code, max_iter=30, layer_checks=args.layer_checks,
+                                                                  post_bits=args.post_bits, msg_bits=args.msg_bits),
+                                          code, batch, dev)
             t_w, n_w = time.perf_counter(), 0
             while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
                 for leg in legs.values():
@@ -99,7 +112,7 @@ def main():
                 leg.totals.zero_()
             torch.cuda.synchronize(dev)
             ev = []
-            for _ in range(args.steps):  # the two schedules alternate inside one window
+            for _ in range(args.steps):  # the decoders alternate inside one window
                 for name, leg in legs.items():
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
@@ -122,15 +135,21 @@ def main():
                     "decoded_frames_per_s": round(decoded / med * 1e3, 1), "mean_iters": round(float(tot[3]) / float(tot[2]), 3),
                     "frame_errors": int(tot[1]) // args.steps, "bit_errors": int(tot[0]) // args.steps, **common}
                 assert int(tot[2]) == batch * args.steps
-                print(json.dumps(rows[name]), flush=True)
-            f, l = rows["flooding"], rows["layered"]
-            print(json.dumps({
-                "config": cfg, "ebn0_db": ebn0, "ratio": "layered / flooding",
-                "frames_per_s": round(l["frames_per_s"] / f["frames_per_s"], 4),
-                "decoded_frames_per_s": (round(l["decoded_frames_per_s"] / f["decoded_frames_per_s"], 4)
-                                         if f["decoded_frames"] else None),
-                "mean_iters": round(l["mean_iters"] / f["mean_iters"], 4),
-                "frame_errors": [l["frame_errors"], f["frame_errors"]], **common}), flush=True)
+            f = rows["flooding"]
+            for name, row in rows.items():  # every layered line carries its ratio to flooding (None: flooding decodes no frame)
+                if name != "flooding":
+                    row["decoded_frames_per_s_vs_flooding"] = (round(row["decoded_frames_per_s"] / f["decoded_frames_per_s"], 4)
+                                                               if f["decoded_frames"] else None)
+                print(json.dumps(row), flush=True)
+            for name in list(legs)[1:]:
+                l = rows[name]
+                print(json.dumps({
+                    "config": cfg, "ebn0_db": ebn0, "ratio": f"{name} / flooding", "describe": l["describe"],
+                    "frames_per_s": round(l["frames_per_s"] / f["frames_per_s"], 4),
+                    "decoded_frames_per_s": (round(l["decoded_frames_per_s"] / f["decoded_frames_per_s"], 4)
+                                             if f["decoded_frames"] else None),
+                    "mean_iters": round(l["mean_iters"] / f["mean_iters"], 4),
+                    "frame_errors": [l["frame_errors"], f["frame_errors"]], **common}), flush=True)
 
 
 if __name__ == "__main__":
