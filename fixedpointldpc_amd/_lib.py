@@ -128,6 +128,7 @@ def lib():
         "fpldpc_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
         "fpldpc_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult), P]),
         "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
+        "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("FPLDPC_LIB_PATH") and not hasattr(L, name):
@@ -154,6 +155,7 @@ EXPORTED = [
     "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_destroy", "fpldpc_layered_describe",
     "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
+    "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
 ]
 
 

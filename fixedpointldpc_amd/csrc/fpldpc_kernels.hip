@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "fpldpc_internal.hpp"
+#include "fpldpc_testing.h"
 
 
 namespace fpldpc {
@@ -893,9 +894,13 @@ __device__ __forceinline__ void lds_add_at(uint32_t addr, int v) {
 
 // Output k of a check: magnitude o, sign = parity of the other inputs' flags = (S ^ flag_k) in bits
 // 15 / 31; st (the v2c in sign-magnitude) is overwritten with the carry-form c2v (o ^ neg) - neg.
-template <bool ASM_OR = false>
+// TRACK = false: the magnitude is not OR-ed into ovor (the caller bounds every output of the check
+// from two chain values instead, ArrayChecks::kChainGuard).
+template <bool ASM_OR = false, bool TRACK = true>
 __device__ __forceinline__ void emit_c2v(uint32_t &st, uint32_t o, uint32_t S, uint32_t &ovor) {
-    if (ASM_OR)
+    if (!TRACK)
+        ;
+    else if (ASM_OR)
         asm("v_or_b32 %0, %0, %1" : "+v"(ovor) : "v"(o));  // not fused into v_or3_b32 (VOP3)
     else
         ovor |= o;
@@ -986,9 +991,29 @@ struct ArrayChecks {
     }
     // One flooding step for this lane's checks: gather from buffer pc, update, scatter-add into
     // buffer pn (LDS byte addresses).  par: bit 15 / 31 = OR over the lane's checks
-    // of each check's syndrome parity for the low / high frame; ovor |= every c2v magnitude.
-    __device__ __forceinline__ void step(const KArgs &a, const uint32_t *, uint32_t *, uint32_t pc, uint32_t pn, u16x2 C2,
-                                         uint32_t M2, uint32_t &par, uint32_t &ovor) {
+    // of each check's syndrome parity for the low / high frame; ovor |= every c2v magnitude, or
+    // (kChainGuard) a bound on them all.
+    //
+    // The chain guard.  bp_mag(a, b) <= min(a, b) + C (packed_cmax), so along the fold
+    //   F_j <= F_{j-1} + C,  B_j <= B_{j+1} + C,  c2v_k = F_{k-1} [+] B_{k+1} <= min(F_{k-1}, B_{k+1}) + C,
+    // and with the middle slot L = (P-1)/2: c2v_k <= F_{L-1} + (k-L+1) C for k >= L (k = P-1: c2v =
+    // F_{P-2} <= F_{L-1} + (P-1-L) C) and c2v_k <= B_{L+1} + (L-k+1) C for 1 <= k <= L (k = 0: c2v =
+    // B_1 <= B_{L+1} + L C).  Every output magnitude of the check is therefore at most
+    //   max(F_{L-1}, B_{L+1}) + G,  G = (L+1) C,
+    // and ovor |= (F_{L-1} + G) | (B_{L+1} + G) has a bit at or above 2^b (cmax = 2^b - 1) whenever
+    // some c2v does: the deferred range test flags every frame the per-output OR would, and possibly a
+    // few more (max(F, B) within G of the threshold), which the int32 kernel then decodes -- exactly, as
+    // any flagged frame.  Both sums stay inside their 16-bit halves (chain values < 2^15, G <= 2^12).
+    // choose_kernel takes this form only while G <= (cmax + 1) / 8; the per-output form is
+    // ArrayChecksOutGuard's kernel.
+    static constexpr bool kChainGuard = kStoreOffs;
+    __device__ __forceinline__ void step(const KArgs &a, const uint32_t *pcp, uint32_t *pnp, uint32_t pc, uint32_t pn,
+                                         u16x2 C2, uint32_t M2, uint32_t &par, uint32_t &ovor) {
+        step_g<kChainGuard>(a, pcp, pnp, pc, pn, C2, M2, par, ovor);
+    }
+    template <bool CHAIN>
+    __device__ __forceinline__ void step_g(const KArgs &a, const uint32_t *, uint32_t *, uint32_t pc, uint32_t pn, u16x2 C2,
+                                           uint32_t M2, uint32_t &par, uint32_t &ovor) {
         uint32_t fail = 0;  // OR over the lane's checks of each check's parity (not their XOR)
         // (literal operands: the same mask constants in VGPRs measured the same, profiles/r2/ab/bp_form.txt)
         constexpr uint32_t SGN = 0x80008000u, MAG = 0x7fff7fffu;
@@ -1168,6 +1193,10 @@ struct ArrayChecks {
                 if (j < L) FB[j] = bp_mag2<kBp>(FB[j - 1], stq[j] & MAG, C2, M2);
                 FB[P - 1 - j] = bp_mag2<kBp>(FB[P - j], stq[P - 1 - j] & MAG, C2, M2);
             }
+            if constexpr (CHAIN) {  // the range guard: a bound on every output from F_{L-1} and B_{L+1}
+                const uint32_t G = W(C2) * (uint32_t)(L + 1);  // (L+1) C in both halves
+                ovor |= (FB[L - 1] + G) | (FB[L + 1] + G);
+            }
             // opaque: recompute st & MAG below instead of keeping 46 masked copies live
 #pragma unroll
             for (int k = 0; k < P; ++k) asm volatile("" : "+v"(stq[k]));
@@ -1180,7 +1209,7 @@ struct ArrayChecks {
                 const uint32_t o = bp_mag2<kBp>(FB[L - 1], FB[L + 1], C2, M2);
                 F = bp_mag2<kBp>(FB[L - 1], aL, C2, M2);
                 B = bp_mag2<kBp>(FB[L + 1], aL, C2, M2);
-                emit_c2v<true>(stq[L], o, S, ovor);
+                emit_c2v<true, !CHAIN>(stq[L], o, S, ovor);
             }
             unsigned short uf = tL, ub = tL;
             if (!kStoreOffs && !kLdsOffs) asm volatile("" : "+v"(uf), "+v"(ub));
@@ -1207,7 +1236,7 @@ struct ArrayChecks {
                         o = bp_mag2<kBp>(F, FB[kf + 1], C2, M2);
                         F = bp_mag2<kBp>(F, stq[kf] & MAG, C2, M2);
                     }
-                    emit_c2v<true>(stq[kf], o, S, ovor);
+                    emit_c2v<true, !CHAIN>(stq[kf], o, S, ovor);
                     if (!kStoreOffs && !kLdsOffs) {
                         uf = (unsigned short)(uf + step4);
                         uf = __builtin_elementwise_min(uf, (unsigned short)(uf - wrap4));
@@ -1224,7 +1253,7 @@ struct ArrayChecks {
                         o = bp_mag2<kBp>(FB[kb - 1], B, C2, M2);
                         B = bp_mag2<kBp>(B, stq[kb] & MAG, C2, M2);
                     }
-                    emit_c2v<true>(stq[kb], o, S, ovor);
+                    emit_c2v<true, !CHAIN>(stq[kb], o, S, ovor);
                     if (!kStoreOffs && !kLdsOffs) {
                         ub = (unsigned short)(ub - step4);
                         ub = __builtin_elementwise_min(ub, (unsigned short)(ub + wrap4));
@@ -1394,6 +1423,17 @@ struct ArrayChecks {
                 lds_add_at(soff(P - 1 - j, pn) + (P - 1 - j) * P * 4, (int)(S[j] - (uint32_t)lo) >> 16);
             }
         }
+    }
+};
+
+// The A policy with the per-output range guard (every c2v magnitude OR-ed into ovor): the same
+// kernel for parameter sets whose G = (L+1) C is too large a share of cmax for the chain guard
+// (large FRAC_WIDTH; choose_kernel).
+template <int P>
+struct ArrayChecksOutGuard : ArrayChecks<P> {
+    __device__ __forceinline__ void step(const KArgs &a, const uint32_t *pcp, uint32_t *pnp, uint32_t pc, uint32_t pn,
+                                         u16x2 C2, uint32_t M2, uint32_t &par, uint32_t &ovor) {
+        this->template step_g<false>(a, pcp, pnp, pc, pn, C2, M2, par, ovor);
     }
 };
 
@@ -2881,6 +2921,8 @@ typedef void (*KernelFn)(KArgs);
 // takes the kernel's host stub from here, so launches and occupancy queries reach this code object.
 // (const void *: KArgs lives in each translation unit's unnamed namespace)
 const void *array47_pair_kernel() { return reinterpret_cast<const void *>(&flood_pk<ArrayChecks<47>, 3>); }
+// the same kernel with the per-output range guard (ArrayChecksOutGuard)
+const void *array47_pair_outguard_kernel() { return reinterpret_cast<const void *>(&flood_pk<ArrayChecksOutGuard<47>, 3>); }
 #else
 // fpldpc_kernels_w1.hip: this file with FPLDPC_TU_TABLE1 = 1 holds the degree-sorted packed table
 // kernel (the W configuration's, flood_pk<TableChecks<8, 4, 7, 3>, 4>) and nothing else, so that it
@@ -2893,6 +2935,7 @@ const void *table8_pair_kernel() { return reinterpret_cast<const void *>(&flood_
 }  // namespace
 // the A and W kernels' host stubs (fpldpc_kernels_a1.hip, fpldpc_kernels_w1.hip, compiled separately)
 const void *array47_pair_kernel();
+const void *array47_pair_outguard_kernel();
 const void *table8_pair_kernel();
 namespace {
 
@@ -2912,6 +2955,7 @@ struct VariantInfo {
     int dmin = 2;           // smallest check degree the variant handles
     int tab_words = 0;      // LDS table words per check after the control words (array LDS offsets)
     int lo_passes = 0;      // > 0: checks listed by ascending degree, the first lo_passes * nt of degree dmin
+    int chain_guard = 0;    // > 0: range guard from two chain values, needs chain_guard * C <= (cmax + 1) / 8
 };
 
 size_t variant_lds(const VariantInfo &x, const fpldpc_code &c) {
@@ -2923,7 +2967,12 @@ size_t variant_lds(const VariantInfo &x, const fpldpc_code &c) {
 }
 
 const VariantInfo kVariants[] = {
-    {Variant::kArray47x2, reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_kernel())), 47, kNT, true, false, "flood_array2<P=47,W=3>", 47, true, Variant::kArray47},
+    // A: the chain range guard (G = 24 C) while it is a small share of cmax, else the same kernel with
+    // the per-output guard (chain_guard_ok)
+    {Variant::kArray47x2, reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_kernel())), 47, kNT, true, false,
+     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47, kNT, false, 2, 0, 0, (47 - 1) / 2 + 1},
+    {Variant::kArray47x2og, reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_outguard_kernel())), 47, kNT, true, false,
+     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47},
     // array codes with up to 1536 checks (R: 1128): 2 checks per lane in one 768-thread workgroup,
     // 3 waves / SIMD (168 VGPRs; the few spills sit in the per-step control code, not in the check
     // update).  SIMD loads 5 / 5 / 4 / 4 check-units per step, as with 3 checks per lane at 2 waves
@@ -2989,6 +3038,13 @@ uint32_t packed_cmax(const fpldpc_code &code, int C) {
     return cm;
 }
 
+// The chain range guard (ArrayChecks::kChainGuard) flags a frame when max(F_{L-1}, B_{L+1}) + G reaches
+// cmax + 1, G = (L+1) C: needlessly only when that maximum lies within G of the threshold.  It is used
+// while G is at most an eighth of the range (C = 10: 240 of 4096); beyond that the per-output guard.
+bool chain_guard_ok(int slots, int C, uint32_t cmax) {
+    return (uint64_t)slots * (uint64_t)C <= ((uint64_t)cmax + 1) / 8;
+}
+
 // flood_lds16 is exact while |v2c| < 2^14 (checked per step): its chain values and c2v are then at
 // most 2^14 - 1 + C, which its u16 minima and int16 c2v state hold while C <= 2^14 (FRAC_WIDTH <= 14).
 constexpr int kLds16MaxC = 1 << 14;
@@ -3034,6 +3090,7 @@ int choose_kernel(const fpldpc_code &code, int device, int mask, int C, KernelCh
         if (x.regular ? !(regular && actual_dc == x.dc) : actual_dc > x.dc) continue;
         if (code.m > x.max_m) continue;
         if (x.lo_passes && !(min_dc == x.dmin && n_min_dc >= x.lo_passes * x.nt)) continue;
+        if (x.chain_guard && !chain_guard_ok(x.chain_guard, C, cmax)) continue;
         pick = &x;
         break;
     }
@@ -3246,4 +3303,13 @@ int launch_decode_frame(const LaunchArgs &la, const EdgeTables &t, int32_t *edge
 }
 
 }  // namespace fpldpc
+
+// Test-only (include/fpldpc_testing.h): the range parameters choose_kernel derives, without a device.
+extern "C" uint32_t fpldpc_testing_range_guard(int32_t dv_max, int32_t C, int32_t slots, int32_t *chain_guard) {
+    fpldpc_code code;
+    code.dv_max = dv_max;
+    const uint32_t cmax = fpldpc::packed_cmax(code, C);
+    if (chain_guard) *chain_guard = cmax > 0 && fpldpc::chain_guard_ok(slots, C, cmax);
+    return cmax;
+}
 #endif  // FPLDPC_TU_ARRAY1 || FPLDPC_TU_TABLE1

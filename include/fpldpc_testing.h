@@ -22,6 +22,12 @@ extern "C" {
  *                    attempts RCCL too (it would not), so the AUTO fallback runs on a one-GPU box. */
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init);
 
+/* The int16 range parameters the kernel choice derives for a code whose largest variable degree is
+ * dv_max at Constant C (no device needed): returns cmax, the largest c2v magnitude the packed kernels
+ * accept (0: none), and in *chain_guard whether an array check of `slots` = (P+1)/2 fold steps takes
+ * the range guard from two chain values (G = slots * C <= (cmax + 1) / 8) rather than per output. */
+uint32_t fpldpc_testing_range_guard(int32_t dv_max, int32_t C, int32_t slots, int32_t *chain_guard);
+
 #ifdef __cplusplus
 }
 #endif
