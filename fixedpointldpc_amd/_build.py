@@ -24,6 +24,7 @@ SOURCES = [
     # the layered decoder: not in DEVICE_TUS / HASHED_TUS -- the build id covers the kernels with committed counters
     "fpldpc_layered.cpp",
     "fpldpc_layered.hip",
+    "fpldpc_layered_minsum.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

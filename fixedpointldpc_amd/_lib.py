@@ -104,6 +104,8 @@ def lib():
         "fpldpc_code_layering": (ctypes.c_int, [P, I32, P]),
         "fpldpc_layered_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, ctypes.POINTER(P)]),
         "fpldpc_layered_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, ctypes.POINTER(P)]),
+        "fpldpc_layered_create_minsum": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, I32,
+                                                        ctypes.POINTER(P)]),
         "fpldpc_layered_destroy": (ctypes.c_int, [P]),
         "fpldpc_layered_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
         "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
@@ -152,7 +154,7 @@ EXPORTED = [
     "fpldpc_encoder_dims", "fpldpc_encoder_info_index", "fpldpc_unpack_info_bytes", "fpldpc_encoder_encode_host",
     "fpldpc_encoder_free", "fpldpc_encoder_encode", "fpldpc_channel_llr",
     "fpldpc_decode_float", "fpldpc_decode_float_host",
-    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_destroy", "fpldpc_layered_describe",
+    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_create_minsum", "fpldpc_layered_destroy", "fpldpc_layered_describe",
     "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
@@ -409,10 +411,18 @@ class LayeredDecoder:
     """fpldpc_layered_t: the layered (row-serial) schedule of the fixed-point decoder, batched on the
     GPU.  layer_checks = 0 picks the layer size (Code.layering).  Same outputs as Decoder.
     post_bits / msg_bits (both 0: nothing saturated) give the saturated decoder of
-    fpldpc_layered_create_sat, which is defined for every input."""
+    fpldpc_layered_create_sat, which is defined for every input.  check="minsum" (with both widths;
+    scale_16 / 16 and offset correct the minimum) gives the min-sum decoder with compressed check state
+    of fpldpc_layered_create_minsum; check="sxor", the default, is the reference's box-plus fold."""
 
     def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
-                 layer_checks=0, post_bits=0, msg_bits=0):
+                 layer_checks=0, post_bits=0, msg_bits=0, check="sxor", scale_16=16, offset=0):
+        if check not in ("sxor", "minsum"):
+            raise ValueError(f"check must be 'sxor' or 'minsum', not {check!r}")
+        if check == "minsum" and (post_bits == 0 or msg_bits == 0):
+            raise ValueError("check='minsum' needs post_bits and msg_bits")
+        if check == "sxor" and (scale_16 != 16 or offset != 0):
+            raise ValueError("scale_16 and offset belong to check='minsum'")
         p = Params()
         lib().fpldpc_params_default(ctypes.byref(p))
         p.max_iter, p.frac_bits, p.width_mask = max_iter, frac_bits, width_mask
@@ -420,7 +430,10 @@ class LayeredDecoder:
         self.code = code
         self.params = p
         h = ctypes.c_void_p()
-        if post_bits == 0 and msg_bits == 0:
+        if check == "minsum":
+            _check(lib().fpldpc_layered_create_minsum(code._h, ctypes.byref(p), layer_checks, post_bits, msg_bits,
+                                                      scale_16, offset, ctypes.byref(h)))
+        elif post_bits == 0 and msg_bits == 0:
             _check(lib().fpldpc_layered_create(code._h, ctypes.byref(p), layer_checks, ctypes.byref(h)))
         else:
             _check(lib().fpldpc_layered_create_sat(code._h, ctypes.byref(p), layer_checks, post_bits, msg_bits,

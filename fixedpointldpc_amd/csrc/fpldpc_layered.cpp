@@ -53,9 +53,13 @@ int constant_c(int frac_bits) { return (int)((5.0 / 8.0) * (1 << frac_bits)); }
 
 int sat_limit(int bits) { return (1 << (bits - 1)) - 1; }
 
-// sat: fpldpc_layered_create_sat (post_bits / msg_bits are validated before anything touches HIP).
-int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, bool sat, int32_t post_bits,
-           int32_t msg_bits, fpldpc_layered_t *out) {
+// The three creation entry points (the arguments of the saturated and the min-sum decoder are validated
+// before anything touches HIP).
+enum Kind { kUnsat, kSat, kMinsum };
+
+int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, Kind kind, int32_t post_bits,
+           int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out) {
+    const bool sat = kind == kSat;
     if (!code || !out) return fail(FPLDPC_ERR_ARG, "null argument");
     fpldpc_params p;
     fpldpc_params_default(&p);
@@ -73,6 +77,15 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
                                             std::to_string(constant_c(p.frac_bits)) + ")");
         const char *state = getenv("FPLDPC_LAYERED_STATE");  // diagnostic: int32 state where int16 would be chosen
         mode = post_bits <= 16 && !(state && !strcmp(state, "i32")) ? kLaySat16 : kLaySat32;
+    }
+    if (kind == kMinsum) {
+        // S_p > S_m keeps the sign of a pinned posterior minus its own message (at most S_m); int16 state
+        if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 16))
+            return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 2 <= msg_bits < post_bits <= 16");
+        if (scale_16 < 1 || scale_16 > 16) return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 1 <= scale_16 <= 16");
+        if (offset < 0 || offset > sat_limit(msg_bits))
+            return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
+        mode = kLayMinsum;
     }
     int L = 0, layers = 0;
     int st = code_layering(*code, layer_checks, &L, &layers);
@@ -92,9 +105,13 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
     d->device = dev;
     d->L = L;
     d->layers = layers;
-    d->post_bits = sat ? post_bits : 0;
-    d->msg_bits = sat ? msg_bits : 0;
-    st = layered_choose(d->code, L, dev, mode, &d->lc);
+    d->post_bits = kind != kUnsat ? post_bits : 0;
+    d->msg_bits = kind != kUnsat ? msg_bits : 0;
+    if (kind == kMinsum) {
+        d->scale_16 = scale_16;
+        d->offset = offset;
+    }
+    st = kind == kMinsum ? layered_minsum_choose(d->code, L, dev, &d->lc) : layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
     const fpldpc_code &c = d->code;
     std::vector<uint8_t> cdeg(c.m);
@@ -123,12 +140,17 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
 extern "C" {
 
 int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, fpldpc_layered_t *out) {
-    return create(code, params, layer_checks, false, 0, 0, out);
+    return create(code, params, layer_checks, kUnsat, 0, 0, 0, 0, out);
 }
 
 int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, int32_t post_bits,
                               int32_t msg_bits, fpldpc_layered_t *out) {
-    return create(code, params, layer_checks, true, post_bits, msg_bits, out);
+    return create(code, params, layer_checks, kSat, post_bits, msg_bits, 0, 0, out);
+}
+
+int fpldpc_layered_create_minsum(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, int32_t post_bits,
+                                 int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out) {
+    return create(code, params, layer_checks, kMinsum, post_bits, msg_bits, scale_16, offset, out);
 }
 
 int fpldpc_layered_destroy(fpldpc_layered_t dec) {
@@ -140,7 +162,10 @@ int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
     const int w = snprintf(buf, cap, "%s L=%d layers=%d grid=%d threads=%d lds=%zu device=%d", dec->lc.name, dec->L,
                            dec->layers, dec->lc.grid, dec->lc.threads, dec->lc.lds_bytes, dec->device);
-    if (dec->lc.mode != kLayUnsat && w > 0 && (size_t)w < cap)
+    if (dec->lc.mode == kLayMinsum && w > 0 && (size_t)w < cap)
+        snprintf(buf + w, cap - w, " sat=%d/%d ms=%d/16-%d state=compressed", dec->post_bits, dec->msg_bits, dec->scale_16,
+                 dec->offset);
+    else if (dec->lc.mode != kLayUnsat && w > 0 && (size_t)w < cap)
         snprintf(buf + w, cap - w, " sat=%d/%d state=%s", dec->post_bits, dec->msg_bits,
                  dec->lc.mode == kLaySat16 ? "i16" : "i32");
     return FPLDPC_OK;
@@ -214,6 +239,7 @@ int fpldpc_layered_decode(fpldpc_layered_t dec, const void *llr, int32_t llr_typ
         a.sat_post = sat_limit(dec->post_bits);
         a.sat_msg = sat_limit(dec->msg_bits);
     }
+    if (dec->lc.mode == kLayMinsum) return layered_minsum_launch(dec->lc, a, dec->scale_16, dec->offset, stream);
     return layered_launch(dec->lc, a, stream);
 }
 

@@ -42,14 +42,10 @@
 #include <string>
 #include <utility>
 
-#include "fpldpc_layered.hpp"
+#include "fpldpc_layered_device.hpp"
 
 namespace fpldpc {
 namespace {
-
-constexpr int kLayMaxNT = 256;  // largest workgroup (4 waves); a decoder uses min(256, L rounded up to 64)
-constexpr int kLayMisc = 4;     // per-workgroup control words after the posteriors: [0] frame, [1] bit errors
-constexpr size_t kLdsMax = 160 * 1024;
 
 // State of a kernel instantiation (MODE): the type of the posteriors and c2v; the clamps run in the two
 // saturated modes.
@@ -59,8 +55,6 @@ template <> struct LayState<kLaySat16> { using type = int16_t; };
 constexpr size_t lay_state_bytes(int mode) { return mode == kLaySat16 ? sizeof(int16_t) : sizeof(int32_t); }
 // 32-bit words that n posteriors take in front of the control words
 __host__ __device__ constexpr size_t lay_post_words(int mode, int n) { return ((size_t)n * lay_state_bytes(mode) + 3) / 4; }
-
-__device__ __forceinline__ int lay_clamp(int x, int S) { return min(max(x, -S), S); }
 
 // x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
 // fpldpc_kernels.hip: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
@@ -73,78 +67,6 @@ __device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
     const int p2 = max(C - d, 0);
     const int r = min(a, b) + p1 - p2;
     return ((x > 0) == (y > 0)) ? r : -r;
-}
-
-__device__ __forceinline__ int lay_load_llr(const LayeredArgs &a, size_t i) {
-    return a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];
-}
-
-// 1 if some check is unsatisfied by hard[v] = post[v] > 0 ? 0 : 1 (workgroup-uniform; a barrier).
-// cdeg: the degree table (LDS), unused when every check has degree DC (EXACT).
-template <int DC, bool EXACT, typename ST>
-__device__ __forceinline__ int lay_syndrome(const LayeredArgs &a, const uint16_t *vidx, const uint8_t *cdeg,
-                                            const ST *post) {
-    const int m = a.m, p = a.array_p;
-    int fail = 0;
-    for (int c = threadIdx.x; c < m; c += blockDim.x) {
-        const int deg = EXACT ? DC : (int)cdeg[c];
-        int ci = 0, col = 0;
-        if (!vidx) {
-            ci = c / p;
-            col = c - ci * p;
-        }
-        int par = 0;
-        for (int k = 0; k < deg; ++k) {
-            const int v = vidx ? (int)vidx[(size_t)k * m + c] : k * p + col;
-            col += ci;
-            if (col >= p) col -= p;
-            par ^= post[v] <= 0;
-        }
-        fail |= par;
-    }
-    return __syncthreads_or(fail);
-}
-
-// Frame epilogue: posteriors, packed hard decisions, per-frame bit errors and totals
-// ({bit errors, frames with errors, frames, iteration sum}, added to).
-template <typename ST>
-__device__ __forceinline__ void lay_store(const LayeredArgs &a, int cw, const ST *post, bool write_post, int iters,
-                                          int ok, int *misc) {
-    const int n = a.n, NT = blockDim.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (a.post && write_post)
-        for (int v = tid; v < n; v += NT) a.post[(size_t)cw * n + v] = post[v];
-    if (a.hard) {
-        uint32_t *h = a.hard + (size_t)cw * a.hard_words;
-        for (int base = wave * 64; base < n; base += NT) {
-            const int v = base + lane;
-            const unsigned long long b = __ballot(v < n && post[v] <= 0);
-            if (lane == 0) {
-                const int w = base >> 5;
-                h[w] = (uint32_t)b;
-                if (w + 1 < a.hard_words) h[w + 1] = (uint32_t)(b >> 32);
-            }
-        }
-    }
-    int errors = 0;
-    if (a.k_info > 0) {
-        int e = 0;
-        for (int i = tid; i < a.k_info; i += NT) e += ((post[a.info_idx[i]] <= 0) ? 1 : 0) != a.info_bits[i];
-        if (e) atomicAdd(&misc[1], e);
-        __syncthreads();
-        errors = misc[1];
-    }
-    if (tid == 0) {
-        if (a.iters) a.iters[cw] = iters;
-        if (a.syn_ok) a.syn_ok[cw] = (uint8_t)ok;
-        if (a.bit_errors) a.bit_errors[cw] = errors;
-        if (a.totals) {
-            atomicAdd(&a.totals[0], (unsigned long long)errors);
-            atomicAdd(&a.totals[1], (unsigned long long)(errors > 0));
-            atomicAdd(&a.totals[2], 1ull);
-            atomicAdd(&a.totals[3], (unsigned long long)iters);
-        }
-    }
 }
 
 // LDS: post [n] ST (up to a whole word) | misc [kLayMisc] | (LDS_STATE) c2v [dc_max][m] ST
@@ -265,6 +187,8 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
 
 using LayeredFn = void (*)(LayeredArgs);
 
+}  // namespace
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per kernel function and device, not per decoder: only
 // ever raise it, so that a later decoder with a smaller code does not take away what an earlier one
 // launches with.  Called with the decoder's device current.
@@ -282,7 +206,7 @@ hipError_t raise_dynamic_lds(const void *fn, size_t bytes) {
     return e;
 }
 
-constexpr int kExactDc = 47;  // the straight-line instantiation: the p = 47 array codes (A, R)
+namespace {
 
 template <int MODE>
 LayeredFn layered_fn_of(int dc, bool lds_state, bool exact) {

@@ -1,5 +1,6 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
-// (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* C ABI) and fpldpc_layered.hip (kernels).
+// (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* C ABI), fpldpc_layered.hip and
+// fpldpc_layered_minsum.hip (kernels).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
 // c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding
@@ -17,8 +18,9 @@ namespace fpldpc {
 int code_layering(const fpldpc_code &code, int layer_checks, int *L, int *layers);
 
 // State of a layered decoder: nothing saturated (fpldpc_layered_create: int32 posteriors and c2v), or
-// the clamps of fpldpc_layered_create_sat with int32 state (post_bits 17..24) or int16 state (<= 16).
-enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2 };
+// the clamps of fpldpc_layered_create_sat with int32 state (post_bits 17..24) or int16 state (<= 16), or
+// fpldpc_layered_create_minsum (int16 posteriors, 16 bytes of state per check: fpldpc_layered_minsum.hip).
+enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3 };
 
 // Kernel choice of a layered decoder, made once at creation.
 struct LayeredChoice {
@@ -66,6 +68,11 @@ struct LayeredArgs {
 // Envelope and kernel choice for (code, L, mode) on `device`; FPLDPC_ERR_UNSUPPORTED outside the envelope.
 int layered_choose(const fpldpc_code &code, int L, int device, int mode, LayeredChoice *out);
 int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
+// The same pair for the min-sum decoder (mode kLayMinsum; lds_state is always true, there is no scratch).
+int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out);
+int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// Raises a kernel's dynamic-LDS limit on the current device, never lowers it (fpldpc_layered.hip).
+hipError_t raise_dynamic_lds(const void *fn, size_t bytes);
 
 }  // namespace fpldpc
 
@@ -75,7 +82,8 @@ struct fpldpc_layered {
     fpldpc_params params{};
     int device = 0;
     int L = 0, layers = 0;
-    int post_bits = 0, msg_bits = 0;  // fpldpc_layered_create_sat; 0: unsaturated
+    int post_bits = 0, msg_bits = 0;  // fpldpc_layered_create_sat / _minsum; 0: unsaturated
+    int scale_16 = 16, offset = 0;    // fpldpc_layered_create_minsum
     fpldpc::LayeredChoice lc;
     uint16_t *d_vidx = nullptr;
     uint8_t *d_cdeg = nullptr;

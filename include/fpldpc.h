@@ -226,6 +226,36 @@ int fpldpc_layered_create(fpldpc_code_t code, const fpldpc_params *params, int32
  * and state=i16|i32), set_reference, decode and decode_host below apply unchanged. */
 int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks,
                               int32_t post_bits, int32_t msg_bits, fpldpc_layered_t *out);
+/* The layered min-sum decoder: the saturated schedule above with the check rule layered hardware runs,
+ * normalised / offset min-sum, in place of the sxor fold.  With S_p, S_m and clamp as above and
+ * f(x) = max(((x * scale_16) >> 4) - offset, 0) for x >= 0, per frame
+ *     post[v] = clamp(LLR[v], S_p);  c2v[c][k] = 0
+ *     for it = 1 .. max_iter, for each check c in code order:
+ *         t[k]   = clamp(post[v_k] - c2v[c][k], S_m)                 (k < deg)
+ *         s[k]   = t[k] <= 0          (the reference's sgn(0) = -1, the same rule as the hard decision)
+ *         m1     = min_k |t[k]|,  k1 = a slot attaining it,  m2 = min_{k != k1} |t[k]|
+ *         mag[k] = f(k == k1 ? m2 : m1)
+ *         new[k] = (parity of s[j] over j != k) ? -mag[k] : mag[k]
+ *         c2v[c][k] = new[k];  post[v_k] = clamp(t[k] + new[k], S_p)
+ * Which slot is k1 on a tie changes no output: then m2 = m1.  scale_16 = 16, offset = 0 is plain min-sum,
+ * which is the saturated decoder above at frac_bits = 0 (C = 0: sxor is sign * min) bit for bit.
+ * Everything else is as in the saturated decoder: hard decision, syndrome, iters, early termination,
+ * precheck on the clamped LLRs with post left untouched, layers as parallelism, outputs (post is int32).
+ * Bounds: 0 <= f(x) <= x, so |c2v| <= S_m, |post| <= S_p, and in registers |post - c2v| <= S_p + S_m and
+ * |t + new| <= 2 S_m, for every input.
+ * FPLDPC_ERR_ARG (with a message, tested before a HIP device is looked for) unless
+ *     2 <= msg_bits < post_bits <= 16,   1 <= scale_16 <= 16,   0 <= offset <= S_m.
+ * S_p > S_m keeps the sign of a pinned posterior minus its own message; the on-chip state is int16.
+ * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
+ * use them.  On chip a check keeps 16 bytes whatever its degree -- f(m1), f(m2), k1 and a 64-bit sign
+ * word, from which every c2v[c][k] is rebuilt -- so there is no per-edge state and no global scratch.
+ * Check degrees 2..64; any code whose int16 posteriors and 16 (17 with mixed degrees) bytes per check fit 160 KiB.
+ * The object is an fpldpc_layered_t like any other: destroy, set_reference, decode and decode_host apply
+ * unchanged; describe names the kernel layered_minsum<..> and ends with
+ * " sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed". */
+int fpldpc_layered_create_minsum(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks,
+                                 int32_t post_bits, int32_t msg_bits, int32_t scale_16, int32_t offset,
+                                 fpldpc_layered_t *out);
 int fpldpc_layered_destroy(fpldpc_layered_t dec);
 /* Kernel variant, L, layers, resident workgroups, threads, LDS bytes. */
 int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap);

@@ -11,11 +11,13 @@ schedules alternate step by step inside one timed window, and the median step is
 
 --post-bits / --msg-bits add a third decoder to the same window: the saturated layered decoder
 (fpldpc_layered_create_sat) at those widths.  R (4096 frames, 6.5 dB) is measured on request
-(--config R): its unsaturated layered line is only as good as int32 holds at that SNR.  The
-FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
+(--config R): its unsaturated layered line is only as good as int32 holds at that SNR.
+--minsum SCALE16 OFFSET (with the two widths) adds the layered min-sum decoder with compressed check
+state (fpldpc_layered_create_minsum) as a further leg; every point then ends with one line that sets its
+step time against the saturated sxor decoder's.  The FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
 
 usage: tools/bench_layered.py [--config A W] [--steps 30] [--warmup 5] [--layer-checks 0]
-                              [--post-bits 12 --msg-bits 10]
+                              [--post-bits 12 --msg-bits 10 [--minsum 12 0]]
 """
 import argparse
 import json
@@ -75,9 +77,12 @@ def main():
     ap.add_argument("--layer-checks", type=int, default=0)
     ap.add_argument("--post-bits", type=int, default=0, help="with --msg-bits: also time the saturated layered decoder")
     ap.add_argument("--msg-bits", type=int, default=0)
+    ap.add_argument("--minsum", type=int, nargs=2, metavar=("SCALE16", "OFFSET"),
+                    help="with --post-bits / --msg-bits: also time the layered min-sum decoder")
     ap.add_argument("--git-head", default=None, help="recorded as git_head where the tree is not a git checkout")
     args = ap.parse_args()
     assert args.steps >= 20, "at least 20 timed steps"
+    assert not args.minsum or (args.post_bits and args.msg_bits), "--minsum needs --post-bits and --msg-bits"
 
     import torch
 
@@ -102,6 +107,11 @@ def main():
                 legs["layered_sat"] = Leg(torch, F.LayeredDecoder(code, max_iter=30, layer_checks=args.layer_checks,
                                                                   post_bits=args.post_bits, msg_bits=args.msg_bits),
                                           code, batch, dev)
+            if args.minsum:
+                legs["layered_minsum"] = Leg(torch, F.LayeredDecoder(code, max_iter=30, layer_checks=args.layer_checks,
+                                                                     check="minsum", post_bits=args.post_bits,
+                                                                     msg_bits=args.msg_bits, scale_16=args.minsum[0],
+                                                                     offset=args.minsum[1]), code, batch, dev)
             t_w, n_w = time.perf_counter(), 0
             while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
                 for leg in legs.values():
@@ -150,6 +160,15 @@ def main():
                                              if f["decoded_frames"] else None),
                     "mean_iters": round(l["mean_iters"] / f["mean_iters"], 4),
                     "frame_errors": [l["frame_errors"], f["frame_errors"]], **common}), flush=True)
+            if args.minsum:  # the yardstick of the min-sum kernel: the saturated sxor decoder at the same widths
+                ms, sx = rows["layered_minsum"], rows["layered_sat"]
+                print(json.dumps({
+                    "config": cfg, "ebn0_db": ebn0, "ratio": "layered_minsum / layered_sat", "describe": ms["describe"],
+                    "median_ms": [ms["median_ms"], sx["median_ms"]], "step_time": round(ms["median_ms"] / sx["median_ms"], 4),
+                    "mean_iters": [ms["mean_iters"], sx["mean_iters"]],
+                    "ms_per_iteration": [round(ms["median_ms"] / ms["mean_iters"], 4), round(sx["median_ms"] / sx["mean_iters"], 4)],
+                    "decoded_frames_per_s_vs_flooding": [ms["decoded_frames_per_s_vs_flooding"],
+                                                         sx["decoded_frames_per_s_vs_flooding"]], **common}), flush=True)
 
 
 if __name__ == "__main__":
