@@ -25,6 +25,8 @@ SOURCES = [
     "fpldpc_layered.cpp",
     "fpldpc_layered.hip",
     "fpldpc_layered_minsum.hip",
+    # the flooding min-sum decoder: as the layered units, outside the build id
+    "fpldpc_minsum.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -111,6 +111,12 @@ def lib():
         "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
         "fpldpc_layered_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
         "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
+        "fpldpc_minsum_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, ctypes.POINTER(P)]),
+        "fpldpc_minsum_destroy": (ctypes.c_int, [P]),
+        "fpldpc_minsum_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
+        "fpldpc_minsum_set_reference": (ctypes.c_int, [P, P, P, I32]),
+        "fpldpc_minsum_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
+        "fpldpc_minsum_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
         "fpldpc_rng_skip": (I64, [I64, U64]),
         "fpldpc_channel_llr_host": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, P,
                                                    I32, I32]),
@@ -156,6 +162,8 @@ EXPORTED = [
     "fpldpc_decode_float", "fpldpc_decode_float_host",
     "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_create_minsum", "fpldpc_layered_destroy", "fpldpc_layered_describe",
     "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
+    "fpldpc_minsum_create", "fpldpc_minsum_destroy", "fpldpc_minsum_describe", "fpldpc_minsum_set_reference",
+    "fpldpc_minsum_decode", "fpldpc_minsum_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
 ]
@@ -415,6 +423,11 @@ class LayeredDecoder:
     scale_16 / 16 and offset correct the minimum) gives the min-sum decoder with compressed check state
     of fpldpc_layered_create_minsum; check="sxor", the default, is the reference's box-plus fold."""
 
+    _abi = "fpldpc_layered"  # the entry points the shared methods below call (MinSumDecoder: fpldpc_minsum)
+
+    def _fn(self, name):
+        return getattr(lib(), f"{self._abi}_{name}")
+
     def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
                  layer_checks=0, post_bits=0, msg_bits=0, check="sxor", scale_16=16, offset=0):
         if check not in ("sxor", "minsum"):
@@ -443,21 +456,21 @@ class LayeredDecoder:
 
     def describe(self):
         buf = ctypes.create_string_buffer(256)
-        _check(lib().fpldpc_layered_describe(self._h, buf, 256))
+        _check(self._fn("describe")(self._h, buf, 256))
         return buf.value.decode()
 
     def set_reference(self, info_index, info_bits):
         idx = np.ascontiguousarray(info_index, np.int32)
         bits = np.ascontiguousarray(info_bits, np.uint8)
-        _check(lib().fpldpc_layered_set_reference(self._h, _ptr(idx), _ptr(bits), len(idx)))
+        _check(self._fn("set_reference")(self._h, _ptr(idx), _ptr(bits), len(idx)))
 
     def decode_ptrs(self, llr_ptr, llr_type, batch, hard=0, iters=0, syn_ok=0, post=0, bit_errors=0, totals=0,
                     stream=0):
         """Asynchronous decode on device pointers (ints); stream is a hipStream_t as int."""
         c = ctypes.c_void_p
-        _check(lib().fpldpc_layered_decode(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
-                                           c(syn_ok or None), c(post or None), c(bit_errors or None),
-                                           c(totals or None), c(stream or None)))
+        _check(self._fn("decode")(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
+                                  c(syn_ok or None), c(post or None), c(bit_errors or None), c(totals or None),
+                                  c(stream or None)))
 
     decode_torch = Decoder.decode_torch  # the same tensor plumbing over this class's decode_ptrs
 
@@ -476,8 +489,8 @@ class LayeredDecoder:
                 (B, self.code.n), np.int32)
         be = np.zeros(B, np.int32) if bit_errors else None
         tot = None if totals is None else np.ascontiguousarray(totals, np.int64)
-        _check(lib().fpldpc_layered_decode_host(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok),
-                                                _ptr(post_arr), _ptr(be), _ptr(tot)))
+        _check(self._fn("decode_host")(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok), _ptr(post_arr),
+                                       _ptr(be), _ptr(tot)))
         out = {"hard": hard, "iters": iters, "syndrome_ok": ok}
         if post_arr is not None:
             out["post"] = post_arr
@@ -489,8 +502,28 @@ class LayeredDecoder:
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
-            _lib.fpldpc_layered_destroy(self._h)
+            getattr(_lib, f"{self._abi}_destroy")(self._h)
             self._h = None
+
+
+class MinSumDecoder(LayeredDecoder):
+    """fpldpc_minsum_t: normalised / offset min-sum (scale_16 / 16 and offset correct the minimum) with the
+    clamps and the compressed check state of the layered min-sum decoder, on the flooding schedule.
+    Defined for every input.  Same outputs and methods as Decoder / LayeredDecoder."""
+
+    _abi = "fpldpc_minsum"
+
+    def __init__(self, code, max_iter=30, early_term=True, precheck=False, device=-1, post_bits=12, msg_bits=10,
+                 scale_16=16, offset=0):
+        p = Params()
+        lib().fpldpc_params_default(ctypes.byref(p))
+        p.max_iter, p.early_term, p.precheck, p.device = max_iter, int(bool(early_term)), int(bool(precheck)), device
+        self.code = code
+        self.params = p
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_minsum_create(code._h, ctypes.byref(p), post_bits, msg_bits, scale_16, offset, ctypes.byref(h)))
+        self._h = h
+        self.hard_words = (code.n + 31) // 32
 
 
 class Encoder:

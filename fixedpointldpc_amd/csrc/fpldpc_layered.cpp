@@ -55,7 +55,8 @@ int sat_limit(int bits) { return (1 << (bits - 1)) - 1; }
 
 // The three creation entry points (the arguments of the saturated and the min-sum decoder are validated
 // before anything touches HIP).
-enum Kind { kUnsat, kSat, kMinsum };
+// kFlood: the flooding min-sum decoder (fpldpc_minsum_create) over the same object; layer_checks unused.
+enum Kind { kUnsat, kSat, kMinsum, kFlood };
 
 int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, Kind kind, int32_t post_bits,
            int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out) {
@@ -87,8 +88,16 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
             return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
         mode = kLayMinsum;
     }
-    int L = 0, layers = 0;
-    int st = code_layering(*code, layer_checks, &L, &layers);
+    if (kind == kFlood) {
+        if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 16))
+            return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 2 <= msg_bits < post_bits <= 16");
+        if (scale_16 < 1 || scale_16 > 16) return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 1 <= scale_16 <= 16");
+        if (offset < 0 || offset > sat_limit(msg_bits))
+            return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
+        mode = kFloodMinsum;
+    }
+    int L = code->m, layers = 1;  // flooding: every check of the frame in one step
+    int st = kind == kFlood ? 0 : code_layering(*code, layer_checks, &L, &layers);
     if (st) return st;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -107,11 +116,13 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
     d->layers = layers;
     d->post_bits = kind != kUnsat ? post_bits : 0;
     d->msg_bits = kind != kUnsat ? msg_bits : 0;
-    if (kind == kMinsum) {
+    if (kind == kMinsum || kind == kFlood) {
         d->scale_16 = scale_16;
         d->offset = offset;
     }
-    st = kind == kMinsum ? layered_minsum_choose(d->code, L, dev, &d->lc) : layered_choose(d->code, L, dev, mode, &d->lc);
+    st = kind == kFlood    ? flood_minsum_choose(d->code, dev, &d->lc)
+         : kind == kMinsum ? layered_minsum_choose(d->code, L, dev, &d->lc)
+                           : layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
     const fpldpc_code &c = d->code;
     std::vector<uint8_t> cdeg(c.m);
@@ -240,6 +251,7 @@ int fpldpc_layered_decode(fpldpc_layered_t dec, const void *llr, int32_t llr_typ
         a.sat_msg = sat_limit(dec->msg_bits);
     }
     if (dec->lc.mode == kLayMinsum) return layered_minsum_launch(dec->lc, a, dec->scale_16, dec->offset, stream);
+    if (dec->lc.mode == kFloodMinsum) return flood_minsum_launch(dec->lc, a, dec->scale_16, dec->offset, stream);
     return layered_launch(dec->lc, a, stream);
 }
 
@@ -295,6 +307,56 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
     if (d_tot) HIP_TRY(hipMemcpyAsync(totals, d_tot, 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return FPLDPC_OK;
+}
+
+// The flooding min-sum decoder (fpldpc_minsum_t): the same object in mode kFloodMinsum behind a handle type
+// of its own, so that staging, reference bits and the argument struct exist once.
+
+int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                         int32_t scale_16, int32_t offset, fpldpc_minsum_t *out) {
+    if (!out) return fail(FPLDPC_ERR_ARG, "null argument");
+    fpldpc_layered_t lay = nullptr;
+    const int st = create(code, params, 0, kFlood, post_bits, msg_bits, scale_16, offset, &lay);
+    if (st) return st;
+    *out = new fpldpc_minsum{lay};
+    return FPLDPC_OK;
+}
+
+int fpldpc_minsum_destroy(fpldpc_minsum_t dec) {
+    if (!dec) return FPLDPC_OK;
+    free_layered(dec->lay);
+    delete dec;
+    return FPLDPC_OK;
+}
+
+int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap) {
+    if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
+    const fpldpc_layered *d = dec->lay;
+    snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d ms=%d/16-%d state=compressed", d->lc.name,
+             d->lc.grid, d->lc.threads, d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits, d->scale_16, d->offset);
+    return FPLDPC_OK;
+}
+
+int fpldpc_minsum_set_reference(fpldpc_minsum_t dec, const int32_t *info_index, const uint8_t *info_bits, int32_t k) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "bad reference");
+    return fpldpc_layered_set_reference(dec->lay, info_index, info_bits, k);
+}
+
+int fpldpc_minsum_decode(fpldpc_minsum_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                         int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors, int64_t *totals,
+                         void *stream) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "null decoder");
+    if (bit_errors && dec->lay->k_info == 0)
+        return fail(FPLDPC_ERR_ARG, "bit_errors requested without fpldpc_minsum_set_reference");
+    return fpldpc_layered_decode(dec->lay, llr, llr_type, batch, hard, iters, syndrome_ok, post, bit_errors, totals, stream);
+}
+
+int fpldpc_minsum_decode_host(fpldpc_minsum_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                              int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors, int64_t *totals) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "null decoder");
+    if (bit_errors && dec->lay->k_info == 0)
+        return fail(FPLDPC_ERR_ARG, "bit_errors requested without fpldpc_minsum_set_reference");
+    return fpldpc_layered_decode_host(dec->lay, llr, llr_type, batch, hard, iters, syndrome_ok, post, bit_errors, totals);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
-// (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* C ABI), fpldpc_layered.hip and
-// fpldpc_layered_minsum.hip (kernels).
+// (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* and fpldpc_minsum_* C ABI), fpldpc_layered.hip,
+// fpldpc_layered_minsum.hip and fpldpc_minsum.hip (kernels).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
 // c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding
@@ -20,7 +20,9 @@ int code_layering(const fpldpc_code &code, int layer_checks, int *L, int *layers
 // State of a layered decoder: nothing saturated (fpldpc_layered_create: int32 posteriors and c2v), or
 // the clamps of fpldpc_layered_create_sat with int32 state (post_bits 17..24) or int16 state (<= 16), or
 // fpldpc_layered_create_minsum (int16 posteriors, 16 bytes of state per check: fpldpc_layered_minsum.hip).
-enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3 };
+// kFloodMinsum is not a layered decoder: the flooding min-sum decoder (fpldpc_minsum_t, fpldpc_minsum.hip)
+// shares this object's host plumbing (L = m, layers = 1, no meaning).
+enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3, kFloodMinsum = 4 };
 
 // Kernel choice of a layered decoder, made once at creation.
 struct LayeredChoice {
@@ -71,6 +73,9 @@ int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *strea
 // The same pair for the min-sum decoder (mode kLayMinsum; lds_state is always true, there is no scratch).
 int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out);
 int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// The same pair for the flooding min-sum decoder (mode kFloodMinsum, fpldpc_minsum.hip): no layers, no scratch.
+int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out);
+int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
 // Raises a kernel's dynamic-LDS limit on the current device, never lowers it (fpldpc_layered.hip).
 hipError_t raise_dynamic_lds(const void *fn, size_t bytes);
 
@@ -95,4 +100,9 @@ struct fpldpc_layered {
     hipStream_t stream = nullptr;  // fpldpc_layered_decode_host staging
     void *d_stage = nullptr;
     size_t stage_bytes = 0;
+};
+
+// Flooding min-sum decoder object (fpldpc_minsum_t): a type of its own in the C ABI over the same plumbing.
+struct fpldpc_minsum {
+    fpldpc_layered *lay = nullptr;  // mode kFloodMinsum, owned
 };

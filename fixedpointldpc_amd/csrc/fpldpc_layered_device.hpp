@@ -1,6 +1,7 @@
 // fpldpc_layered_device.hpp -- device code the layered kernels share (fpldpc_layered.hip: the sxor fold;
-// fpldpc_layered_minsum.hip: min-sum with compressed check state): the frame framework's constants, the
-// LLR load, the syndrome and the frame epilogue.  Included by those two translation units only.
+// fpldpc_layered_minsum.hip: min-sum with compressed check state; fpldpc_minsum.hip: the same rule on the
+// flooding schedule): the frame framework's constants, the LLR load, the syndrome and the frame epilogue.
+// Included by those three translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -271,6 +271,56 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
                                int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors,
                                int64_t *totals);
 
+/* ---------------------------------------------------------------- flooding min-sum decoder */
+/* Normalised / offset min-sum, saturated and defined for every input, on the flooding schedule: the check
+ * rule, the clamps and the compressed check state of fpldpc_layered_create_minsum, with every check of a
+ * step reading the same posteriors (the schedule of fpldpc_decode).  S_p = 2^(post_bits-1) - 1,
+ * S_m = 2^(msg_bits-1) - 1, clamp(x, S) = min(max(x, -S), S) and f(x) = max(((x * scale_16) >> 4) - offset, 0)
+ * are those of the layered min-sum decoder.  Per frame
+ *     L[v] = clamp(LLR[v], S_p);  post[v] = L[v];  c2v[c][k] = 0
+ *     for it = 1 .. max_iter:
+ *         for every check c, all reading the same post (no order between checks):
+ *             t[k]   = clamp(post[v_k] - c2v[c][k], S_m)                  (k < deg)
+ *             s[k]   = t[k] <= 0
+ *             m1 = min_k |t[k]|,  k1 = a slot attaining it,  m2 = min_{k != k1} |t[k]|
+ *             new[k] = (parity of s[j], j != k) ? -f(k == k1 ? m2 : m1) : f(k == k1 ? m2 : m1)
+ *             c2v[c][k] = new[k]
+ *         for every variable v:  post[v] = clamp(L[v] + sum of c2v[c][k] over the edges (c, k) with v_k = v, S_p)
+ *         hard[v] = post[v] > 0 ? 0 : 1;  the syndrome over clist;  iters = it;  with early_term stop on a pass
+ * With params.precheck the syndrome of the clamped LLRs is tested first; on a pass the frame returns 0
+ * iterations with the channel decision and post is left untouched.  Outputs as fpldpc_decode (post is int32,
+ * totals are ADDED to).
+ * scale_16 = 16, offset = 0 at widths where no clamp acts (clipped values: none) is fpldpc_decode at
+ * frac_bits = 0 bit for bit: there the reference's Constant is 0 and its sxor is sign * min.
+ * Bounds, for every input: |c2v| <= S_m, |post| <= S_p, |post - c2v| <= S_p + S_m and
+ * |L + sum| <= S_p + dv_max * S_m (an int32 accumulator on chip; its sign is the posterior's).
+ * FPLDPC_ERR_ARG (with a message, tested before a HIP device is looked for) unless
+ *     2 <= msg_bits < post_bits <= 16,   1 <= scale_16 <= 16,   0 <= offset <= S_m.
+ * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
+ * use them.  On chip a check keeps 16 bytes whatever its degree, as in the layered min-sum decoder; there is
+ * no per-edge state and no global scratch for any code.  Envelope: check degrees 2..64 and 14 n + 17 m + 32
+ * bytes (three int32 accumulators, the int16 LLRs, the state and the degrees; the index table joins them only
+ * where it fits) within the CU's 160 KiB of LDS; outside it FPLDPC_ERR_UNSUPPORTED (with a message).
+ * FPLDPC_ERR_HIP without a HIP device. */
+typedef struct fpldpc_minsum *fpldpc_minsum_t;
+int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                         int32_t scale_16, int32_t offset, fpldpc_minsum_t *out);
+int fpldpc_minsum_destroy(fpldpc_minsum_t dec);
+/* "flood_minsum<DC=..,addr=computed|table|gtable,deg=exact|table> grid=N threads=N lds=N device=N
+ * sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed". */
+int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap);
+/* As fpldpc_set_reference. */
+int fpldpc_minsum_set_reference(fpldpc_minsum_t dec, const int32_t *info_index, const uint8_t *info_bits, int32_t k);
+/* Conventions and outputs as fpldpc_layered_decode: device pointers, asynchronous on `stream`, any output
+ * may be NULL, I32 / I16 LLRs, totals ADDED to; one object per stream (its calls share one work counter). */
+int fpldpc_minsum_decode(fpldpc_minsum_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                         int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors, int64_t *totals,
+                         void *stream);
+/* Same on host buffers (synchronous; stages through device memory owned by the decoder). */
+int fpldpc_minsum_decode_host(fpldpc_minsum_t dec, const void *llr, int32_t llr_type, int32_t batch, uint32_t *hard,
+                              int32_t *iters, uint8_t *syndrome_ok, int32_t *post, int32_t *bit_errors,
+                              int64_t *totals);
+
 /* ---------------------------------------------------------------- channel model */
 /* Lehmer state after `draws` calls of Random() from `seed` (rngs.cpp:52-69, a = 48271,
  * m = 2^31 - 1): seed * a^draws mod m. */

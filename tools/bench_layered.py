@@ -14,10 +14,12 @@ schedules alternate step by step inside one timed window, and the median step is
 (--config R): its unsaturated layered line is only as good as int32 holds at that SNR.
 --minsum SCALE16 OFFSET (with the two widths) adds the layered min-sum decoder with compressed check
 state (fpldpc_layered_create_minsum) as a further leg; every point then ends with one line that sets its
-step time against the saturated sxor decoder's.  The FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
+step time against the saturated sxor decoder's.  --flood-minsum SCALE16 OFFSET (with the two widths) adds the
+flooding min-sum decoder (fpldpc_minsum_create) to the same window, on the same frames with the same outputs
+and totals, and a line that sets it against layered min-sum when both run.  The FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
 
 usage: tools/bench_layered.py [--config A W] [--steps 30] [--warmup 5] [--layer-checks 0]
-                              [--post-bits 12 --msg-bits 10 [--minsum 12 0]]
+                              [--post-bits 12 --msg-bits 10 [--minsum 12 0] [--flood-minsum 12 0]]
 """
 import argparse
 import json
@@ -79,10 +81,13 @@ def main():
     ap.add_argument("--msg-bits", type=int, default=0)
     ap.add_argument("--minsum", type=int, nargs=2, metavar=("SCALE16", "OFFSET"),
                     help="with --post-bits / --msg-bits: also time the layered min-sum decoder")
+    ap.add_argument("--flood-minsum", type=int, nargs=2, metavar=("SCALE16", "OFFSET"),
+                    help="with --post-bits / --msg-bits: also time the flooding min-sum decoder")
     ap.add_argument("--git-head", default=None, help="recorded as git_head where the tree is not a git checkout")
     args = ap.parse_args()
     assert args.steps >= 20, "at least 20 timed steps"
     assert not args.minsum or (args.post_bits and args.msg_bits), "--minsum needs --post-bits and --msg-bits"
+    assert not args.flood_minsum or (args.post_bits and args.msg_bits), "--flood-minsum needs --post-bits and --msg-bits"
 
     import torch
 
@@ -112,6 +117,10 @@ def main():
                                                                      check="minsum", post_bits=args.post_bits,
                                                                      msg_bits=args.msg_bits, scale_16=args.minsum[0],
                                                                      offset=args.minsum[1]), code, batch, dev)
+            if args.flood_minsum:
+                legs["flood_minsum"] = Leg(torch, F.MinSumDecoder(code, max_iter=30, post_bits=args.post_bits,
+                                                                  msg_bits=args.msg_bits, scale_16=args.flood_minsum[0],
+                                                                  offset=args.flood_minsum[1]), code, batch, dev)
             t_w, n_w = time.perf_counter(), 0
             while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
                 for leg in legs.values():
@@ -169,6 +178,16 @@ def main():
                     "ms_per_iteration": [round(ms["median_ms"] / ms["mean_iters"], 4), round(sx["median_ms"] / sx["mean_iters"], 4)],
                     "decoded_frames_per_s_vs_flooding": [ms["decoded_frames_per_s_vs_flooding"],
                                                          sx["decoded_frames_per_s_vs_flooding"]], **common}), flush=True)
+            if args.flood_minsum and args.minsum:  # the same check rule on the two schedules
+                fm, lm = rows["flood_minsum"], rows["layered_minsum"]
+                print(json.dumps({
+                    "config": cfg, "ebn0_db": ebn0, "ratio": "flood_minsum / layered_minsum", "describe": fm["describe"],
+                    "median_ms": [fm["median_ms"], lm["median_ms"]], "step_time": round(fm["median_ms"] / lm["median_ms"], 4),
+                    "mean_iters": [fm["mean_iters"], lm["mean_iters"]],
+                    "ms_per_iteration": [round(fm["median_ms"] / fm["mean_iters"], 4), round(lm["median_ms"] / lm["mean_iters"], 4)],
+                    "frame_errors": [fm["frame_errors"], lm["frame_errors"]],
+                    "decoded_frames_per_s_vs_flooding": [fm["decoded_frames_per_s_vs_flooding"],
+                                                         lm["decoded_frames_per_s_vs_flooding"]], **common}), flush=True)
 
 
 if __name__ == "__main__":
