@@ -79,22 +79,15 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
         const char *state = getenv("FPLDPC_LAYERED_STATE");  // diagnostic: int32 state where int16 would be chosen
         mode = post_bits <= 16 && !(state && !strcmp(state, "i32")) ? kLaySat16 : kLaySat32;
     }
-    if (kind == kMinsum) {
+    if (kind == kMinsum || kind == kFlood) {
+        const std::string who = kind == kMinsum ? "layered min-sum decoder" : "flooding min-sum decoder";
         // S_p > S_m keeps the sign of a pinned posterior minus its own message (at most S_m); int16 state
         if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 16))
-            return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 2 <= msg_bits < post_bits <= 16");
-        if (scale_16 < 1 || scale_16 > 16) return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 1 <= scale_16 <= 16");
+            return fail(FPLDPC_ERR_ARG, who + ": need 2 <= msg_bits < post_bits <= 16");
+        if (scale_16 < 1 || scale_16 > 16) return fail(FPLDPC_ERR_ARG, who + ": need 1 <= scale_16 <= 16");
         if (offset < 0 || offset > sat_limit(msg_bits))
-            return fail(FPLDPC_ERR_ARG, "layered min-sum decoder: need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
-        mode = kLayMinsum;
-    }
-    if (kind == kFlood) {
-        if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 16))
-            return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 2 <= msg_bits < post_bits <= 16");
-        if (scale_16 < 1 || scale_16 > 16) return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 1 <= scale_16 <= 16");
-        if (offset < 0 || offset > sat_limit(msg_bits))
-            return fail(FPLDPC_ERR_ARG, "flooding min-sum decoder: need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
-        mode = kFloodMinsum;
+            return fail(FPLDPC_ERR_ARG, who + ": need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
+        mode = kind == kMinsum ? kLayMinsum : kFloodMinsum;
     }
     int L = code->m, layers = 1;  // flooding: every check of the frame in one step
     int st = kind == kFlood ? 0 : code_layering(*code, layer_checks, &L, &layers);

@@ -30,19 +30,11 @@
 // with the arithmetic in int32 registers; lanes of a layer write distinct posteriors with native
 // 16-bit LDS stores, so two lanes on the halves of one word never read-modify-write it.  With
 // post_bits 17..24 the state stays int32.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <mutex>
-#include <string>
 #include <utility>
 
-#include "fpldpc_layered_device.hpp"
+#include "fpldpc_layered_host.hpp"
 
 namespace fpldpc {
 namespace {
@@ -104,14 +96,7 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
     }
 
     for (;;) {
-        __syncthreads();
-        if (tid == 0) {
-            const int wi = atomicAdd(&a.counters[0], 1);
-            misc[0] = wi < a.batch ? wi : -1;
-            misc[1] = 0;
-        }
-        __syncthreads();
-        const int cw = misc[0];
+        const int cw = lay_next_frame(a, misc);
         if (cw < 0) break;
         for (int v = tid; v < n; v += NT) {
             int x = lay_load_llr(a, (size_t)cw * n + v);
@@ -177,12 +162,7 @@ __global__ void __launch_bounds__(kLayMaxNT) layered_generic(LayeredArgs a) {
         }
         lay_store(a, cw, post, true, iters, !fail, misc);
     }
-    // the last workgroup out resets the counter block for the next call (every workgroup has made
-    // its last work-counter access, a returning atomic, before counting itself out)
-    if (tid == 0 && atomicAdd(&a.counters[1], 1) == (int)gridDim.x - 1) {
-        a.counters[0] = 0;
-        a.counters[1] = 0;
-    }
+    lay_leave(a);
 }
 
 using LayeredFn = void (*)(LayeredArgs);
@@ -210,15 +190,11 @@ namespace {
 
 template <int MODE>
 LayeredFn layered_fn_of(int dc, bool lds_state, bool exact) {
-    if (exact) return lds_state ? layered_generic<kExactDc, true, true, MODE> : layered_generic<kExactDc, false, true, MODE>;
-    switch (dc) {
-        case 8: return lds_state ? layered_generic<8, true, false, MODE> : layered_generic<8, false, false, MODE>;
-        case 16: return lds_state ? layered_generic<16, true, false, MODE> : layered_generic<16, false, false, MODE>;
-        case 32: return lds_state ? layered_generic<32, true, false, MODE> : layered_generic<32, false, false, MODE>;
-        case 48: return lds_state ? layered_generic<48, true, false, MODE> : layered_generic<48, false, false, MODE>;
-        case 64: return lds_state ? layered_generic<64, true, false, MODE> : layered_generic<64, false, false, MODE>;
-    }
-    return nullptr;
+    return lay_for_dc(dc, exact, [&](auto d, auto e) -> LayeredFn {
+        constexpr int DC = decltype(d)::value;
+        constexpr bool EXACT = decltype(e)::value;
+        return lds_state ? layered_generic<DC, true, EXACT, MODE> : layered_generic<DC, false, EXACT, MODE>;
+    });
 }
 
 LayeredFn layered_fn(int dc, bool lds_state, bool exact, int mode) {
@@ -237,20 +213,11 @@ LayeredFn layered_fn(int dc, bool lds_state, bool exact, int mode) {
 // CU's 160 KiB of LDS: n <= 40956 with int32 state; with int16 state every code object's n (<= 65535:
 // 128 KiB of posteriors) as long as its degree table fits beside them.
 int layered_choose(const fpldpc_code &code, int L, int device, int mode, LayeredChoice *out) {
-    for (int r = 0; r < code.m; r++)
-        if (code.cdeg[r] < 2) return fail(FPLDPC_ERR_UNSUPPORTED, "check of degree < 2 (reference behaviour undefined)");
-    int dc = 0;
-    for (int d : {8, 16, 32, 48, 64})
-        if (!dc && code.dc_max <= d) dc = d;
-    if (!dc) return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: check degree above 64");
+    LayeredChoice lc;
+    if (int st = lay_choice_of_code(code, mode, "layered", &lc)) return st;
     const size_t state = lay_state_bytes(mode);
     if (mode != kLaySat16 && (size_t)(code.n + kLayMisc) * sizeof(int) > kLdsMax)
         return fail(FPLDPC_ERR_UNSUPPORTED, "layered decoder: code length above 40956 (int32 posteriors in 160 KiB of LDS)");
-    LayeredChoice lc;
-    lc.mode = mode;
-    lc.exact = code.regular_checks && code.dc_max == kExactDc;
-    lc.dc = lc.exact ? kExactDc : dc;
-    lc.computed = code.array_forward && code.array_p > 0;
     // posteriors and control words, plus one byte per check for the degree table
     const size_t base = (lay_post_words(mode, code.n) + kLayMisc) * sizeof(int) + (lc.exact ? 0 : (size_t)code.m);
     if (base > kLdsMax)
@@ -266,71 +233,39 @@ int layered_choose(const fpldpc_code &code, int L, int device, int mode, Layered
     // LDS, =lds keeps c2v in LDS wherever it fits; FPLDPC_LAYERED_TABLE=global / lds places the index
     // table regardless of the rule above.
     const char *force = getenv("FPLDPC_LAYERED_C2V");
-    const char *table = getenv("FPLDPC_LAYERED_TABLE");
     const bool force_global = force && !strcmp(force, "global"), force_lds = force && !strcmp(force, "lds");
     const size_t c2v_bytes = edges * state, tab_bytes = lc.computed ? 0 : edges * sizeof(uint16_t);
     lc.threads = std::min(kLayMaxNT, (L + 63) / 64 * 64);
     lc.lds_state = base + c2v_bytes <= kLdsMax && !force_global;
-    LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact, mode);
-    // resident workgroups per CU with `lds` bytes of LDS (0 and `e` set on an error)
-    hipError_t e = hipSuccess;
-    auto resident = [&](size_t lds) {
-        int per_cu = 0;
-        if (e == hipSuccess && lds > 64 * 1024) e = raise_dynamic_lds((const void *)fn, lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, lc.threads, lds);
-        return e == hipSuccess ? per_cu : 0;
-    };
+    LayResidency<LayeredFn> resident{layered_fn(lc.dc, lc.lds_state, lc.exact, mode), lc.threads};
     // Saturated decoders: a c2v that fits LDS but leaves one workgroup per CU resident (R with int16
     // state: 110 KB) goes to the global scratch with its 4 workgroups per CU instead -- the kernel runs
     // at the latency of its dependent chain, and one wave per CU hides none of it (measured
     // on R).  The unsaturated decoder keeps its rule: LDS wherever c2v fits.
     if (mode != kLayUnsat && lc.lds_state && !force_lds) {
         const int with_lds = resident(base + c2v_bytes);
-        if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
+        if (resident.e != hipSuccess) return fail_hip(resident.e, "layered kernel occupancy");
         if (with_lds < 2) {
             lc.lds_state = false;
-            fn = layered_fn(lc.dc, false, lc.exact, mode);
+            resident.fn = layered_fn(lc.dc, false, lc.exact, mode);
         }
     }
-    if (lc.lds_state && tab_bytes && base + c2v_bytes + tab_bytes <= kLdsMax) {
-        if (table && (!strcmp(table, "lds") || !strcmp(table, "global")))
-            lc.table_lds = !strcmp(table, "lds");
-        else
-            lc.table_lds = resident(base + c2v_bytes + tab_bytes) == resident(base + c2v_bytes);
-        if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
-    }
+    lc.table_lds = lc.lds_state && lay_table_in_lds("FPLDPC_LAYERED_TABLE", base + c2v_bytes, tab_bytes, resident);
     lc.lds_bytes = base + (lc.lds_state ? c2v_bytes + (lc.table_lds ? tab_bytes : 0) : 0);
     int per_cu = resident(lc.lds_bytes);
-    if (e != hipSuccess) return fail_hip(e, "layered kernel occupancy");
-    if (per_cu < 1) return fail(FPLDPC_ERR_UNSUPPORTED, "layered kernel cannot be resident (occupancy 0)");
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
     // global c2v: at most 4 workgroups per CU, so that the scratch (R: 212 KB per workgroup, 106 KB with
     // int16 state) stays within the L2 / Infinity Cache
     if (!lc.lds_state) per_cu = std::min(per_cu, 4);
-    lc.grid = per_cu * prop.multiProcessorCount;
+    if (int st = lay_grid(per_cu, resident.e, device, "layered", &lc.grid)) return st;
     lc.scratch_bytes = lc.lds_state ? 0 : (size_t)lc.grid * edges * state;
     snprintf(lc.name, sizeof lc.name, "%s<DC=%d,c2v=%s,addr=%s,deg=%s>", mode == kLayUnsat ? "layered_generic" : "layered_sat",
-             lc.dc, lc.lds_state ? "lds" : "global", lc.computed ? "computed" : lc.table_lds ? "table" : "gtable",
-             lc.exact ? "exact" : "table");
+             lc.dc, lc.lds_state ? "lds" : "global", lay_addr_name(lc), lc.exact ? "exact" : "table");
     *out = lc;
     return FPLDPC_OK;
 }
 
 int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream) {
-    if (args.batch <= 0) return FPLDPC_OK;
-    const LayeredFn fn = layered_fn(lc.dc, lc.lds_state, lc.exact, lc.mode);
-    if (!fn) return fail(FPLDPC_ERR_ARG, "layered decoder has no kernel");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fn, dim3(std::min(lc.grid, args.batch)), dim3(lc.threads), lc.lds_bytes, s, args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        // a launch that fails leaves the counter block for the next call to find non-zero: re-zero it
-        (void)hipMemsetAsync(args.counters, 0, kLayeredCounterInts * sizeof(int32_t), s);
-        return fail_hip(e, "layered kernel launch");
-    }
-    return FPLDPC_OK;
+    return lay_launch(layered_fn(lc.dc, lc.lds_state, lc.exact, lc.mode), lc, args, args, stream, "layered");
 }
 
 }  // namespace fpldpc

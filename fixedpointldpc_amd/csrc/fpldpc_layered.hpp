@@ -1,6 +1,7 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
 // (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* and fpldpc_minsum_* C ABI), fpldpc_layered.hip,
-// fpldpc_layered_minsum.hip and fpldpc_minsum.hip (kernels).
+// fpldpc_layered_minsum.hip and fpldpc_minsum.hip (kernels; through fpldpc_layered_device.hpp, beside which
+// fpldpc_layered_host.hpp holds their shared choice and launch steps and fpldpc_minsum_device.hpp the min-sum rule).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
 // c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding

@@ -1,7 +1,8 @@
 // fpldpc_layered_device.hpp -- device code the layered kernels share (fpldpc_layered.hip: the sxor fold;
 // fpldpc_layered_minsum.hip: min-sum with compressed check state; fpldpc_minsum.hip: the same rule on the
-// flooding schedule): the frame framework's constants, the LLR load, the syndrome and the frame epilogue.
-// Included by those three translation units only.
+// flooding schedule): the frame framework's constants, the frame pull and the way out of the kernel, the
+// LLR load, the syndrome and the frame epilogue.  Included by those three translation units (the two
+// min-sum units through fpldpc_minsum_device.hpp, the check rule they share).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,28 @@ __device__ __forceinline__ int lay_clamp(int x, int S) { return min(max(x, -S), 
 
 __device__ __forceinline__ int lay_load_llr(const LayeredArgs &a, size_t i) {
     return a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];
+}
+
+// The next frame of this workgroup from the work counter, or -1 when the batch is taken; clears the frame's
+// bit-error word.  Two barriers: the first keeps the previous frame's readers of misc ahead of the write.
+__device__ __forceinline__ int lay_next_frame(const LayeredArgs &a, int *misc) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int wi = atomicAdd(&a.counters[0], 1);
+        misc[0] = wi < a.batch ? wi : -1;
+        misc[1] = 0;
+    }
+    __syncthreads();
+    return misc[0];
+}
+
+// Leaving the kernel: the last workgroup out resets the counter block for the next call (every workgroup
+// has made its last work-counter access, a returning atomic, before counting itself out).
+__device__ __forceinline__ void lay_leave(const LayeredArgs &a) {
+    if (threadIdx.x == 0 && atomicAdd(&a.counters[1], 1) == (int)gridDim.x - 1) {
+        a.counters[0] = 0;
+        a.counters[1] = 0;
+    }
 }
 
 // 1 if some check is unsatisfied by hard[v] = post[v] > 0 ? 0 : 1 (workgroup-uniform; a barrier).
