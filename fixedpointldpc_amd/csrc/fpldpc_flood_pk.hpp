@@ -1,0 +1,797 @@
+// fpldpc_flood_pk.hpp -- flood_pk, the packed flooding kernel: two frames per lane (one per 16-bit
+// half), the halves refilled independently, a lone last frame continued in the policy's split form.
+// The check side is the policy CK (fpldpc_flood_checks_array.hpp, fpldpc_flood_checks_table.hpp), which
+// the including unit brings itself.  Included by fpldpc_kernels.hip, fpldpc_kernels_a1.hip and
+// fpldpc_kernels_w1.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <type_traits>
+
+#include "fpldpc_flood_device.hpp"
+#include "fpldpc_flood_packed.hpp"
+
+// flood_pk's diagnostic builds (-DFPLDPC_PHASE_TRACE, -DFPLDPC_WAIT_TRACE: tools/wait_trace.py,
+// -DFPLDPC_TAIL_TRACE: tools/tail_trace.py; read with tools/wg_trace.py).  The shipped build defines
+// none of them, and the macros below expand to nothing or to a plain barrier.
+// FPLDPC_PHASE_TRACE: thread 0's s_memrealtime ticks between PH_T0(v) and PH_ADD(acc, v).
+#if FPLDPC_PHASE_TRACE
+#define PH_T0(v) const unsigned long long v = (tid == 0) ? __builtin_amdgcn_s_memrealtime() : 0ull
+#define PH_ADD(acc, v) if (tid == 0) acc += __builtin_amdgcn_s_memrealtime() - v
+#else
+#define PH_T0(v)
+#define PH_ADD(acc, v)
+#endif
+// FPLDPC_WAIT_TRACE = 1: PK_SYNC, the barriers of the packed loop other than the per-step one (refills,
+// stores, the final-update syndrome pass, the range check), adds its wait to wt_bar2.
+// FPLDPC_WAIT_TRACE = 2: word 4 holds the per-step LLR copy instead; 3: everything after the per-step
+// barrier (decisions, stores, refills).
+#if FPLDPC_WAIT_TRACE
+#if FPLDPC_WAIT_TRACE >= 2
+#define PK_SYNC() __syncthreads()
+#else
+#define PK_SYNC()                                                         \
+    do {                                                                  \
+        const unsigned long long pk_t = __builtin_amdgcn_s_memtime();     \
+        __syncthreads();                                                  \
+        wt_bar2 += __builtin_amdgcn_s_memtime() - pk_t;                   \
+    } while (0)
+#endif
+#else
+#define PK_SYNC() __syncthreads()
+#endif
+
+namespace fpldpc {
+namespace {
+
+// (the tail's split step, for the policies that have one)
+template <class CK>
+__device__ __forceinline__ void split_step_of(CK &ck, const uint32_t *pcp, uint32_t *pnp, uint32_t pc, uint32_t pn,
+                                              u16x2 C2, uint32_t M2, uint32_t &par, uint32_t &ovor) {
+    if constexpr (CK::kSplit) ck.split_step(pcp, pnp, pc, pn, C2, M2, par, ovor);
+}
+
+template <class CK, int WAVES, int NT = kNT>
+__global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
+    extern __shared__ __attribute__((aligned(16))) int smem[];
+    const int n = CK::kN ? CK::kN : a.n;
+    uint32_t *const bufs = reinterpret_cast<uint32_t *>(smem);  // 3 x n posteriors, biased pairs
+    uint32_t *const llrc = bufs + 3 * n;                          // n channel LLRs, biased pairs
+    int *const misc = smem + 4 * n;
+    // misc: [0,1] frame of half h (-1 idle)  [2,3] start step  [4,5] load taint  [6..8] flag words
+    //       [12] final-pass syndrome word  [13] deferred range-check word
+    //       [9,10] bit-error accumulators
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u16x2 C2 = (u16x2)(unsigned short)a.C;
+    uint32_t M2 = ((1u << a.bfe_w) - 1u) * 0x10001u;
+    {  // box-plus constants in VGPRs, not SGPRs (bp_mag2)
+        uint32_t c2w = W(C2);
+        asm volatile("" : "+v"(c2w), "+v"(M2));
+        C2 = U2(c2w);
+    }
+
+    for (int v = tid; v < 4 * n; v += NT) bufs[v] = 0x7fff7fffu;  // zero posteriors (biased pairs)
+    if (tid < kMiscInts) misc[tid] = tid < 2 ? -1 : 0;
+    CK ck;
+    ck.init(a, tid, reinterpret_cast<uint32_t *>(smem + 4 * n + kMiscInts));  // (array LDS-offset table)
+    constexpr int kRB = CK::kRefillBatch;  // refill: LLR words per thread in flight (0: one at a time)
+    // kRB > 0: the masked-BER info positions / reference bits ([2][hard_words], the same for every
+    // frame of the call) staged in LDS after the check table, so a frame's store reads no global
+    // memory on its critical path (variant_lds reserves the words)
+    uint32_t *const lmask = reinterpret_cast<uint32_t *>(smem + 4 * n + kMiscInts) + (size_t)a.m * CK::kTabWords;
+    if (kRB > 0 && a.info_mask && a.k_info > 0)
+        for (int i = tid; i < 2 * a.hard_words; i += NT) lmask[i] = a.info_mask[i];
+    uint32_t ovf = 0;
+    bool taint[2] = {false, false};
+    __syncthreads();
+
+    unsigned long long trace_t0 = 0;
+    int trace_frames = 0;  // thread 0: frames pulled (diagnostic trace)
+#if FPLDPC_PHASE_TRACE
+    // diagnostic build only: thread 0's s_memrealtime ticks in the refills, the frame pulls inside
+    // them (FPLDPC_PHASE_TRACE=2: the stores' ballot loops instead; 3: the refills' part up to the
+    // second barrier) and the stores, and the steps run (3: the refills' load loops) (trace words 4..7)
+    unsigned long long ph_refill = 0, ph_pull = 0, ph_store = 0, ph_steps = 0, ph_sloop = 0, ph_rhead = 0, ph_rload = 0;
+#endif
+#if FPLDPC_WAIT_TRACE
+    // diagnostic build only (tools/wait_trace.py): per wave, s_memtime cycles in the packed loop's
+    // check step, at its per-step barrier, and in the whole packed loop, written after the
+    // [grid][8] trace words as [grid][64]: wave w's {step, barrier, loop, steps, other barriers} at
+    // 5w..5w+4 (up to 12 waves)
+    unsigned long long wt_step = 0, wt_bar = 0, wt_loop0 = __builtin_amdgcn_s_memtime(), wt_steps = 0, wt_bar2 = 0;
+#endif
+#if FPLDPC_TAIL_TRACE
+    // diagnostic build only (tools/tail_trace.py): thread 0's s_memrealtime when a pull first found
+    // the queue empty and when the workgroup entered the split tail, and the steps it then ran with
+    // two live frames, one live frame (packed) and in the split form (trace words 4..7)
+    unsigned long long tt_empty = 0, tt_split = 0, tt_two = 0, tt_one = 0, tt_splits = 0;
+#endif
+    // (Re)fill the halves in `mask` before step s: new frames' LLRs into llrc, into the buffer
+    // read at step s (pc) and the one accumulated at step s (pn); c2v state and overflow trackers
+    // of the half cleared.  Uniform control flow (every thread calls it with the same arguments).
+    auto refill = [&](int mask, int s, int cur_next) {
+        PH_T0(ph_r0);
+        // kRB > 0: one atomic for every refilled half, issued before the barrier so that its round
+        // trip overlaps the wait (frames wi, wi + 1 in half order, as two pulls in a row would give)
+        int got[2] = {-1, -1};
+        if (kRB > 0 && tid == 0) {
+            const int wi = atomicAdd(a.work_counter, (mask & 1) + (mask >> 1));
+            const int lim = a.frame_list ? *a.frame_count : a.batch;
+            const int w1 = wi + (mask & 1);
+            if ((mask & 1) && wi < lim) got[0] = a.frame_list ? a.frame_list[wi] : wi;
+            if ((mask & 2) && w1 < lim) got[1] = a.frame_list ? a.frame_list[w1] : w1;
+        }
+        // every wave has finished reading misc[0..3] (finish decision, store) before thread 0
+        // replaces the frame ids and start steps
+        PK_SYNC();
+        if (tid == 0) {
+            misc[13] = 0;  // deferred range-check word (read by every wave before the barrier above)
+            for (int h = 0; h < 2; ++h)
+                if (mask >> h & 1) {
+                    PH_T0(ph_p0);
+                    misc[h] = kRB > 0 ? got[h] : pull_frame(a, a.work_counter);
+                    PH_ADD(ph_pull, ph_p0);
+#if FPLDPC_TAIL_TRACE
+                    if (misc[h] < 0 && !tt_empty) tt_empty = __builtin_amdgcn_s_memrealtime();
+#endif
+                    trace_frames += misc[h] >= 0;
+                    misc[2 + h] = s;
+                    misc[4 + h] = 0;
+                    misc[9 + h] = 0;
+                }
+        }
+        PK_SYNC();
+        PH_ADD(ph_rhead, ph_r0);
+        PH_T0(ph_l0);
+        uint32_t *pc = bufs + cur_next * n;
+        uint32_t *pn = bufs + ((cur_next + 1) % 3) * n;
+        if constexpr (kRB > 0) {
+            // both refilled halves at once, kRB words per thread with their loads in flight
+            // together, one read-modify-write of each LDS word for both halves
+            constexpr int KB = kRB > 0 ? kRB : 1;
+            const int f0 = (mask & 1) ? misc[0] : -1, f1 = (mask & 2) ? misc[1] : -1;
+            bool big0 = false, big1 = false;
+            int v0 = tid;
+            asm volatile("" : "+v"(v0));
+            auto ld = [&](int f, int v) -> int {
+                const size_t i = (size_t)f * n + v;
+                return a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];
+            };
+            for (int vb = v0; vb < n; vb += KB * NT) {
+                int x0[KB], x1[KB];
+#pragma unroll
+                for (int j = 0; j < KB; ++j) {
+                    const int v = vb + j * NT;
+                    x0[j] = (v < n && f0 >= 0) ? ld(f0, v) : 0;
+                    x1[j] = (v < n && f1 >= 0) ? ld(f1, v) : 0;
+                }
+#pragma unroll
+                for (int j = 0; j < KB; ++j) {
+                    const int v = vb + j * NT;
+                    if (v < n) {
+                        if (x0[j] > kLlrMax || x0[j] < -kLlrMax) {
+                            big0 = true;
+                            x0[j] = 0;
+                        }
+                        if (x1[j] > kLlrMax || x1[j] < -kLlrMax) {
+                            big1 = true;
+                            x1[j] = 0;
+                        }
+                        uint32_t L = llrc[v], C = pc[v], N = pn[v];
+                        if (mask & 1) {
+                            L = bias_set(L, 0, x0[j]);
+                            C = bias_set(C, 0, x0[j]);
+                            N = bias_set(N, 0, x0[j]);
+                        }
+                        if (mask & 2) {
+                            L = bias_set(L, 1, x1[j]);
+                            C = bias_set(C, 1, x1[j]);
+                            N = bias_set(N, 1, x1[j]);
+                        }
+                        llrc[v] = L;
+                        pc[v] = C;
+                        pn[v] = N;
+                    }
+                }
+            }
+            if (big0) atomicOr(&misc[4], 1);
+            if (big1) atomicOr(&misc[5], 1);
+        }
+        for (int h = 0; h < 2 && kRB == 0; ++h) {
+            if (!(mask >> h & 1)) continue;
+            const int f = misc[h];
+            bool big = false;
+            // (an opaque start, so the loop's per-lane bounds are not hoisted out of the step loop
+            // and held in VGPRs across it -- A 163 -> 142 VGPRs, +4.7 %; R's spills gone,
+            // profiles/r3/ab/opaque_loops*.txt)
+            int v0 = tid;
+            asm volatile("" : "+v"(v0));
+            for (int v = v0; v < n; v += NT) {
+                int x = 0;
+                if (f >= 0) {
+                    const size_t i = (size_t)f * n + v;
+                    x = a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];
+                    if (x > kLlrMax || x < -kLlrMax) {
+                        big = true;
+                        x = 0;
+                    }
+                }
+                llrc[v] = bias_set(llrc[v], h, x);
+                pc[v] = bias_set(pc[v], h, x);
+                pn[v] = bias_set(pn[v], h, x);
+            }
+            if (big) atomicOr(&misc[4 + h], 1);
+        }
+        PH_ADD(ph_rload, ph_l0);
+        PK_SYNC();
+        PH_ADD(ph_refill, ph_r0);
+    };
+
+    // Outputs of the frame in half h: posteriors / hard decisions from buffer pf (biased pairs),
+    // or the channel decision on a pre-check pass (posteriors left untouched).
+    // calculateBER (ArrayLDPC_Decoder.cpp:707-722) with distinct info positions (a.info_mask) comes
+    // out of the hard-decision ballots: errors = popcount((hard ^ ref) & mask) per 32 variables,
+    // instead of a gather of k_info scattered posteriors and their index / bit tables per frame.
+    // The workgroup's totals are summed in LDS and added to a.totals once, at exit.
+    auto store = [&](int h, const uint32_t *pf, bool pre, int iters, int ok) {
+        PH_T0(ph_s0);
+        const int f = misc[h];
+        int v0 = tid, b0 = wave * 64;  // opaque loop starts (see refill)
+        asm volatile("" : "+v"(v0), "+v"(b0));
+        if (a.post && !pre)
+            for (int v = v0; v < n; v += NT) a.post[(size_t)f * n + v] = bias_half(pf[v], h);
+        const bool masked = a.k_info > 0 && a.info_mask;
+        if (kRB > 0 && (a.hard || masked)) {
+            // kRB > 0: the posterior words of four ballots read together, the info masks from LDS
+            uint32_t *hd = a.hard ? a.hard + (size_t)f * a.hard_words : nullptr;
+            int e = 0;
+            for (int base = b0; base < n; base += 4 * NT) {
+                uint32_t pv[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int v = base + j * NT + lane;
+                    pv[j] = v < n ? pf[v] : 0u;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int bj = base + j * NT;
+                    if (bj >= n) break;
+                    const unsigned long long b = __ballot(bj + lane < n && bias_half(pv[j], h) <= 0);
+                    if (lane == 0) {
+                        const int w = bj >> 5;
+                        const bool two = w + 1 < a.hard_words;
+                        if (hd) {
+                            hd[w] = (uint32_t)b;
+                            if (two) hd[w + 1] = (uint32_t)(b >> 32);
+                        }
+                        if (masked) {
+                            const uint32_t *mk = lmask, *rf = lmask + a.hard_words;
+                            e += __popc(((uint32_t)b ^ rf[w]) & mk[w]);
+                            if (two) e += __popc(((uint32_t)(b >> 32) ^ rf[w + 1]) & mk[w + 1]);
+                        }
+                    }
+                }
+            }
+            if (masked && e) atomicAdd(&misc[9 + h], e);
+            PH_ADD(ph_sloop, ph_s0);
+        } else if (a.hard || masked) {
+            uint32_t *hd = a.hard ? a.hard + (size_t)f * a.hard_words : nullptr;
+            int e = 0;
+            for (int base = b0; base < n; base += NT) {
+                const int v = base + lane;
+                const unsigned long long b = __ballot(v < n && bias_half(pf[v], h) <= 0);
+                if (lane == 0) {
+                    const int w = base >> 5;
+                    const bool two = w + 1 < a.hard_words;
+                    if (hd) {
+                        hd[w] = (uint32_t)b;
+                        if (two) hd[w + 1] = (uint32_t)(b >> 32);
+                    }
+                    if (masked) {
+                        const uint32_t *mk = a.info_mask, *rf = a.info_mask + a.hard_words;
+                        e += __popc(((uint32_t)b ^ rf[w]) & mk[w]);
+                        if (two) e += __popc(((uint32_t)(b >> 32) ^ rf[w + 1]) & mk[w + 1]);
+                    }
+                }
+            }
+            if (masked && e) atomicAdd(&misc[9 + h], e);
+        }
+        int errors = 0;
+        if (a.k_info > 0) {
+            if (!masked) {
+                int e = 0;
+                for (int i = v0; i < a.k_info; i += NT) e += ((bias_half(pf[a.info_idx[i]], h) <= 0) ? 1 : 0) != a.info_bits[i];
+                if (e) atomicAdd(&misc[9 + h], e);
+            }
+            PK_SYNC();
+            errors = misc[9 + h];
+        }
+        if (tid == 0) {
+            if (a.iters) a.iters[f] = iters;
+            if (a.syn_ok) a.syn_ok[f] = (uint8_t)ok;
+            if (a.bit_errors) a.bit_errors[f] = errors;
+            if (a.totals) {
+                misc[kTotW] += errors;
+                misc[kTotW + 1] += errors > 0;
+                misc[kTotW + 2] += 1;
+                misc[kTotW + 3] += iters;
+            }
+        }
+        PH_ADD(ph_store, ph_s0);
+    };
+
+    clock_probe(a, 0);
+    if (a.wgtrace) trace_t0 = __builtin_amdgcn_s_memrealtime();  // every lane: a wave-uniform (SGPR) value
+    refill(3, 1, 0);
+    taint[0] = misc[4] != 0;
+    taint[1] = misc[5] != 0;
+    // Frame ids and start steps of the two halves in (wave-uniform) registers, so the per-step
+    // decisions need one LDS read (the flag word) instead of a chain of dependent ones (A +1.5 %; W
+    // +13.5 % together with the final-update syndrome pass below, profiles/r4/ab/w_regctl.txt --
+    // round 3's table-policy build lost 4 % with it to SGPR spills).
+    int frm_r[2], sst_r[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        frm_r[h] = __builtin_amdgcn_readfirstlane(misc[h]);
+        sst_r[h] = __builtin_amdgcn_readfirstlane(misc[2 + h]);
+    }
+    auto frm = [&](int h) { return frm_r[h]; };
+    auto sst = [&](int h) { return sst_r[h]; };
+    // The steps after whose barrier nothing can happen -- every live half's fail flag set (no
+    // pre-check or early-termination end) and s < q_until (no half at max_iter or one short of it)
+    // -- skip the end decisions: 60-odd scalar instructions per wave and step, which R's twelve
+    // waves (one workgroup per CU) issue one after another on the CU's scalar unit between two
+    // steps (A +2.1 %, A @ 4.5 dB +3.1 %, W +2.8 %, W @ 2 dB +2.0 %, R +1.4 %,
+    // profiles/r6/ab/quick_exit.txt).  q_live: the live halves (bit h), whose fail flags must be set.
+    int q_live = 0, q_until = 0;
+    auto set_quick = [&]() {
+        q_live = (frm(0) >= 0 ? 1 : 0) | (frm(1) >= 0 ? 2 : 0);
+        q_until = 0x7fffffff;
+        for (int h = 0; h < 2; ++h)
+            if (frm(h) >= 0) q_until = min(q_until, sst(h) + a.max_iter - 1);
+    };
+    set_quick();
+    int cur = 0;
+    int s = 1;
+    bool more = true;
+    // (a half goes idle only at a refill: the tail check runs there, and once before the first step)
+    bool tail = CK::kSplit && a.split_tail && (frm(0) < 0) != (frm(1) < 0);
+    for (; !tail; ++s) {
+        if (q_live == 0) {  // both halves idle
+            clock_probe(a, 2);
+            if (a.wgtrace && tid == 0) {
+                unsigned long long *t = a.wgtrace + 8 * (size_t)blockIdx.x;
+                t[0] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) |
+                       (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_XCC_ID, HW_REG_HW_ID
+                t[1] = trace_t0;
+                t[2] = __builtin_amdgcn_s_memrealtime();
+                t[3] = (unsigned long long)trace_frames;
+#if FPLDPC_PHASE_TRACE
+                t[4] = ph_refill;
+                t[5] = FPLDPC_PHASE_TRACE == 3 ? ph_rhead : FPLDPC_PHASE_TRACE == 2 ? ph_sloop : ph_pull;
+                t[6] = ph_store;
+                t[7] = FPLDPC_PHASE_TRACE == 3 ? ph_rload : ph_steps;
+#endif
+#if FPLDPC_TAIL_TRACE
+                t[4] = tt_empty;
+                t[5] = tt_split;
+                t[6] = tt_two | tt_one << 32;
+                t[7] = tt_splits;
+#endif
+            }
+#if FPLDPC_WAIT_TRACE
+            if (a.wgtrace && lane == 0) {
+                unsigned long long *w = a.wgtrace + 8 * (size_t)gridDim.x + 64 * (size_t)blockIdx.x + 5 * wave;
+                w[0] = wt_step;
+                w[1] = wt_bar;
+                w[2] = __builtin_amdgcn_s_memtime() - wt_loop0;
+                w[3] = wt_steps;
+                w[4] = wt_bar2;
+            }
+#endif
+            more = false;
+            break;
+        }
+        const uint32_t *pc = bufs + cur * n;
+        uint32_t *pn = bufs + ((cur + 1) % 3) * n;
+        uint32_t *pr = bufs + ((cur + 2) % 3) * n;
+#if FPLDPC_WAIT_TRACE == 2
+        const unsigned long long wc0 = __builtin_amdgcn_s_memtime();
+#endif
+        {
+            int v0 = tid;  // opaque: keeps the compiler from hoisting 3 x 9 addresses across steps
+            asm volatile("" : "+v"(v0));
+            if (CK::kN) {
+#pragma unroll
+                for (int v = v0, j = 0; j < (CK::kN + NT - 1) / NT; ++j, v += NT)
+                    if (j < CK::kN / NT || v < CK::kN) pr[v] = llrc[v];
+            } else if ((n & 3) == 0) {  // 16-byte chunks, every buffer 16-byte aligned (W +1.3-1.4 %, W @ 2 dB +2.0 %, profiles/r6/ab/w_copy16.txt)
+                const int n4 = n >> 2;
+                const uint4 *l4 = reinterpret_cast<const uint4 *>(llrc);
+                uint4 *p4 = reinterpret_cast<uint4 *>(pr);
+                for (int vb = v0; vb < n4; vb += 2 * NT) {
+                    const uint4 t0 = l4[vb];
+                    uint4 t1 = {};
+                    if (vb + NT < n4) t1 = l4[vb + NT];
+                    p4[vb] = t0;
+                    if (vb + NT < n4) p4[vb + NT] = t1;
+                }
+            } else {  // 8 loads in flight per thread, then 8 stores
+                for (int vb = v0; vb < n; vb += 8 * NT) {
+                    uint32_t t[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) t[j] = vb + j * NT < n ? llrc[vb + j * NT] : 0u;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (vb + j * NT < n) pr[vb + j * NT] = t[j];
+                }
+            }
+        }
+#if FPLDPC_WAIT_TRACE == 2
+        wt_bar2 += __builtin_amdgcn_s_memtime() - wc0;
+#endif
+        // flag word of step s+1: last read at step s-2, and every thread has passed the barrier of
+        // step s-1 since; it is next written after this step's barrier
+        if (tid == 0) {
+#if FPLDPC_PHASE_TRACE
+            ++ph_steps;
+#endif
+#if FPLDPC_TAIL_TRACE
+            if (tt_empty) {
+                if (frm(0) >= 0 && frm(1) >= 0) ++tt_two;
+                else ++tt_one;
+            }
+#endif
+            misc[6 + (s + 1) % 3] = 0;
+            misc[12] = 0;  // flag word of a final-update syndrome pass (below), read after this step's barrier
+        }
+        uint32_t par = 0, ovor = 0;
+        // When every frame in flight is at its last iteration (or the half is idle), this step only
+        // needs the syndrome of pc: the frames end here whatever it says, so the check update into pn
+        // (whose results nobody reads) is skipped -- max_iter updates per frame instead of max_iter + 1.
+#if FPLDPC_WAIT_TRACE
+        const unsigned long long wt0 = __builtin_amdgcn_s_memtime();
+#endif
+        ck.step(a, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
+        ovf |= ovor;
+        // per-step flags: fail (syndrome) for each half, OR over the block.  The int16 range flags
+        // (ovf, sticky per lane until the half is refilled) are reduced only when a frame ends,
+        // below: an overflow taints every frame in flight, and no frame is stored before that check
+        // (two ballots per step instead of four: W +0.6 %, R +0.3 %, A within noise; profiles/r2/ab/flags.txt).
+        {
+            const uint32_t bits = (par >> 15 & 1u) | (par >> 30 & 2u);
+            uint32_t wb = 0;
+#pragma unroll
+            for (int b = 0; b < 2; ++b) wb |= __ballot((bits >> b) & 1u) ? (1u << b) : 0u;
+            if (wb) atomicOr(&misc[6 + s % 3], (int)wb);  // (wave-uniform: the atomic optimizer elects one lane)
+        }
+#if FPLDPC_WAIT_TRACE
+        const unsigned long long wt1 = __builtin_amdgcn_s_memtime();
+        wt_step += wt1 - wt0;
+        ++wt_steps;
+#endif
+        __syncthreads();
+#if FPLDPC_WAIT_TRACE
+        wt_bar += __builtin_amdgcn_s_memtime() - wt1;
+#endif
+#if FPLDPC_WAIT_TRACE == 3
+        const unsigned long long wd0 = __builtin_amdgcn_s_memtime();
+#endif
+        uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane(misc[6 + s % 3]);
+        int finished = 0;
+        if (!((flags & (uint32_t)q_live) == (uint32_t)q_live && s < q_until)) {
+            // When no frame ends on pc's syndrome but every frame still running has just made its last
+            // update (max_iter) into pn, check pn now (one syndrome pass after the barrier) instead of in
+            // the next step's gather: a frame then costs max_iter check updates, not max_iter + 1.
+            const uint32_t *pf = pc;
+            int dadj = 0;
+            {
+                bool any = false, last = true, ends = false;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (frm(h) < 0) continue;
+                    const int d = s - sst(h);
+                    const bool fail = flags >> h & 1u;
+                    ends = ends || (d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter;
+                    any = true;
+                    last = last && d + 1 == a.max_iter;
+                }
+                if (any && last && !ends) {
+                    const uint32_t p2 = ck.syndrome(pn, lds_addr(pn));
+                    const uint32_t b2 = (p2 >> 15 & 1u) | (p2 >> 30 & 2u);
+                    uint32_t w2 = 0;
+                    for (int b = 0; b < 2; ++b) w2 |= __ballot((b2 >> b) & 1u) ? (1u << b) : 0u;
+                    if (lane == 0 && w2) atomicOr(&misc[12], (int)w2);
+                    PK_SYNC();
+                    flags = (flags & ~3u) | (uint32_t)__builtin_amdgcn_readfirstlane(misc[12]);
+                    pf = pn;
+                    dadj = 1;
+                }
+            }
+            int ending = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (frm(h) < 0) continue;
+                const int d = s - sst(h) + dadj;
+                const bool fail = flags >> h & 1u;
+                if ((d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter) ending |= 1 << h;
+            }
+            if (ending) {
+                // the deferred int16 range check: a c2v at or above 2^b (a.cmax = 2^b - 1) in either half
+                // since that half's refill corrupts both halves' posterior words, so it taints every
+                // frame in flight (misc[13] is cleared again by the refill that follows)
+                const uint32_t hi_bits = ~(a.cmax * 0x10001u);
+                if (__ballot((ovf & hi_bits) != 0u) && lane == 0) atomicOr(&misc[13], 1);
+                PK_SYNC();
+                if (__builtin_amdgcn_readfirstlane(misc[13])) {
+                    taint[0] = taint[0] || frm(0) >= 0;
+                    taint[1] = taint[1] || frm(1) >= 0;
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (!(ending >> h & 1)) continue;
+                const int d = s - sst(h) + dadj;  // completed updates in pf for this frame
+                const bool fail = flags >> h & 1u;
+                const bool pre = d == 0 && a.precheck && !fail;
+                finished |= 1 << h;
+                if (taint[h]) {
+                    if (tid == 0) a.fb_list[atomicAdd(a.fb_count, 1)] = frm(h);
+                } else {
+                    store(h, pre ? llrc : pf, pre, pre ? 0 : d, pre ? 1 : !fail);
+                }
+            }
+        }
+        cur = (cur + 1) % 3;
+        if (finished) {
+            refill(finished, s + 1, cur);
+            // the refilled half starts from zero c2v state and a fresh range tracker
+            const uint32_t keep = (finished & 1 ? 0xffff0000u : 0xffffffffu) & (finished & 2 ? 0x0000ffffu : 0xffffffffu);
+            ck.clear(finished);
+            ovf &= keep;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (finished >> h & 1) taint[h] = misc[4 + h] != 0;
+                frm_r[h] = __builtin_amdgcn_readfirstlane(misc[h]);
+                sst_r[h] = __builtin_amdgcn_readfirstlane(misc[2 + h]);
+            }
+            if constexpr (CK::kSplit) tail = a.split_tail && (frm(0) < 0) != (frm(1) < 0);
+            set_quick();
+        }
+#if FPLDPC_WAIT_TRACE == 3
+        wt_bar2 += __builtin_amdgcn_s_memtime() - wd0;
+#endif
+    }
+    // (the split loop's step)
+    auto step_body = [&](int s, auto split_c) -> bool {
+        constexpr bool SPLIT = decltype(split_c)::value;
+        if (frm(0) < 0 && frm(1) < 0) {
+            clock_probe(a, 2);
+            if (a.wgtrace && tid == 0) {
+                unsigned long long *t = a.wgtrace + 8 * (size_t)blockIdx.x;
+                t[0] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) |
+                       (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_XCC_ID, HW_REG_HW_ID
+                t[1] = trace_t0;
+                t[2] = __builtin_amdgcn_s_memrealtime();
+                t[3] = (unsigned long long)trace_frames;
+#if FPLDPC_PHASE_TRACE
+                t[4] = ph_refill;
+                t[5] = FPLDPC_PHASE_TRACE == 3 ? ph_rhead : FPLDPC_PHASE_TRACE == 2 ? ph_sloop : ph_pull;
+                t[6] = ph_store;
+                t[7] = FPLDPC_PHASE_TRACE == 3 ? ph_rload : ph_steps;
+#endif
+#if FPLDPC_TAIL_TRACE
+                t[4] = tt_empty;
+                t[5] = tt_split;
+                t[6] = tt_two | tt_one << 32;
+                t[7] = tt_splits;
+#endif
+            }
+            return false;
+        }
+        const uint32_t *pc = bufs + cur * n;
+        uint32_t *pn = bufs + ((cur + 1) % 3) * n;
+        uint32_t *pr = bufs + ((cur + 2) % 3) * n;
+        {
+            int v0 = tid;  // opaque: keeps the compiler from hoisting 3 x 9 addresses across steps
+            asm volatile("" : "+v"(v0));
+            if (CK::kN) {
+#pragma unroll
+                for (int v = v0, j = 0; j < (CK::kN + NT - 1) / NT; ++j, v += NT)
+                    if (j < CK::kN / NT || v < CK::kN) pr[v] = llrc[v];
+            } else if ((n & 3) == 0) {  // 16-byte chunks, every buffer 16-byte aligned (W +1.3-1.4 %, W @ 2 dB +2.0 %, profiles/r6/ab/w_copy16.txt)
+                const int n4 = n >> 2;
+                const uint4 *l4 = reinterpret_cast<const uint4 *>(llrc);
+                uint4 *p4 = reinterpret_cast<uint4 *>(pr);
+                for (int vb = v0; vb < n4; vb += 2 * NT) {
+                    const uint4 t0 = l4[vb];
+                    uint4 t1 = {};
+                    if (vb + NT < n4) t1 = l4[vb + NT];
+                    p4[vb] = t0;
+                    if (vb + NT < n4) p4[vb + NT] = t1;
+                }
+            } else {  // 8 loads in flight per thread, then 8 stores
+                for (int vb = v0; vb < n; vb += 8 * NT) {
+                    uint32_t t[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) t[j] = vb + j * NT < n ? llrc[vb + j * NT] : 0u;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (vb + j * NT < n) pr[vb + j * NT] = t[j];
+                }
+            }
+        }
+        // flag word of step s+1: last read at step s-2, and every thread has passed the barrier of
+        // step s-1 since; it is next written after this step's barrier
+        if (tid == 0) {
+#if FPLDPC_PHASE_TRACE
+            ++ph_steps;
+#endif
+#if FPLDPC_TAIL_TRACE
+            ++tt_splits;
+#endif
+            misc[6 + (s + 1) % 3] = 0;
+            misc[12] = 0;  // flag word of a final-update syndrome pass (below), read after this step's barrier
+        }
+        uint32_t par = 0, ovor = 0;
+        // When every frame in flight is at its last iteration (or the half is idle), this step only
+        // needs the syndrome of pc: the frames end here whatever it says, so the check update into pn
+        // (whose results nobody reads) is skipped -- max_iter updates per frame instead of max_iter + 1.
+        if constexpr (SPLIT)
+            split_step_of(ck, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
+        else
+            ck.step(a, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
+        ovf |= ovor;
+        // per-step flags: fail (syndrome) for each half, OR over the block.  The int16 range flags
+        // (ovf, sticky per lane until the half is refilled) are reduced only when a frame ends,
+        // below: an overflow taints every frame in flight, and no frame is stored before that check
+        // (two ballots per step instead of four: W +0.6 %, R +0.3 %, A within noise; profiles/r2/ab/flags.txt).
+        {
+            const uint32_t bits = (par >> 15 & 1u) | (par >> 30 & 2u);
+            uint32_t wb = 0;
+#pragma unroll
+            for (int b = 0; b < 2; ++b) wb |= __ballot((bits >> b) & 1u) ? (1u << b) : 0u;
+            if (lane == 0 && wb) atomicOr(&misc[6 + s % 3], (int)wb);
+        }
+        __syncthreads();
+        uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane(misc[6 + s % 3]);
+        {  // the packed loop's quick exit (from the control words: q_live / q_until are the packed loop's)
+            bool q = true;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (frm(h) >= 0) q = q && (flags >> h & 1u) && s < sst(h) + a.max_iter - 1;
+            if (q) {
+                cur = (cur + 1) % 3;
+                return true;
+            }
+        }
+        // When no frame ends on pc's syndrome but every frame still running has just made its last
+        // update (max_iter) into pn, check pn now (one syndrome pass after the barrier) instead of in
+        // the next step's gather: a frame then costs max_iter check updates, not max_iter + 1.
+        const uint32_t *pf = pc;
+        int dadj = 0;
+        {
+            bool any = false, last = true, ends = false;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (frm(h) < 0) continue;
+                const int d = s - sst(h);
+                const bool fail = flags >> h & 1u;
+                ends = ends || (d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter;
+                any = true;
+                last = last && d + 1 == a.max_iter;
+            }
+            if (any && last && !ends) {
+                const uint32_t p2 = ck.syndrome(pn, lds_addr(pn));
+                const uint32_t b2 = (p2 >> 15 & 1u) | (p2 >> 30 & 2u);
+                uint32_t w2 = 0;
+                for (int b = 0; b < 2; ++b) w2 |= __ballot((b2 >> b) & 1u) ? (1u << b) : 0u;
+                if (lane == 0 && w2) atomicOr(&misc[12], (int)w2);
+                __syncthreads();
+                flags = (flags & ~3u) | (uint32_t)__builtin_amdgcn_readfirstlane(misc[12]);
+                pf = pn;
+                dadj = 1;
+            }
+        }
+        int ending = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (frm(h) < 0) continue;
+            const int d = s - sst(h) + dadj;
+            const bool fail = flags >> h & 1u;
+            if ((d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter) ending |= 1 << h;
+        }
+        if (ending) {
+            // the deferred int16 range check: a c2v at or above 2^b (a.cmax = 2^b - 1) in either half
+            // since that half's refill corrupts both halves' posterior words, so it taints every
+            // frame in flight (misc[13] is cleared again by the refill that follows)
+            const uint32_t hi_bits = ~(a.cmax * 0x10001u);
+            if (__ballot((ovf & hi_bits) != 0u) && lane == 0) atomicOr(&misc[13], 1);
+            __syncthreads();
+            if (__builtin_amdgcn_readfirstlane(misc[13])) {
+                taint[0] = taint[0] || frm(0) >= 0;
+                taint[1] = taint[1] || frm(1) >= 0;
+            }
+        }
+        int finished = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (!(ending >> h & 1)) continue;
+            const int d = s - sst(h) + dadj;  // completed updates in pf for this frame
+            const bool fail = flags >> h & 1u;
+            const bool pre = d == 0 && a.precheck && !fail;
+            finished |= 1 << h;
+            if (taint[h]) {
+                if (tid == 0) a.fb_list[atomicAdd(a.fb_count, 1)] = frm(h);
+            } else {
+                store(h, pre ? llrc : pf, pre, pre ? 0 : d, pre ? 1 : !fail);
+            }
+        }
+        cur = (cur + 1) % 3;
+        if (finished) {
+            refill(finished, s + 1, cur);
+            // the refilled half starts from zero c2v state and a fresh range tracker.  (In the split
+            // form the queue is empty -- a half goes idle only when a pull finds it so -- and this
+            // refill finds no frame: the workgroup ends.)
+            const uint32_t keep = (finished & 1 ? 0xffff0000u : 0xffffffffu) & (finished & 2 ? 0x0000ffffu : 0xffffffffu);
+            ck.clear(finished);
+            ovf &= keep;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (finished >> h & 1) taint[h] = misc[4 + h] != 0;
+                frm_r[h] = __builtin_amdgcn_readfirstlane(misc[h]);
+                sst_r[h] = __builtin_amdgcn_readfirstlane(misc[2 + h]);
+            }
+        }
+        return true;
+    };
+    if constexpr (CK::kSplit) {
+        if (more) {
+            // The tail: this frame continues in half 0 of the LDS words with its check split over the
+            // lane halves (ArrayChecks::split_step, about 55 % of the packed step's instructions), so
+            // the frames the launch waits on at its end run at a shorter step latency.  A frame in half
+            // 1 is moved to half 0 first: posterior, next-posterior and LLR words rotated, its control
+            // words swapped.
+            const int h = frm(0) < 0 ? 1 : 0;
+            if (h) {
+                for (int v = tid; v < 4 * n; v += NT) bufs[v] = CK::rot16(bufs[v]);
+                if (tid == 0) {
+                    for (int i : {0, 2, 4, 9}) {
+                        const int t = misc[i];
+                        misc[i] = misc[i + 1];
+                        misc[i + 1] = t;
+                    }
+                }
+                const int f0 = frm_r[0], s0 = sst_r[0];
+                const bool t0 = taint[0];
+                frm_r[0] = frm_r[1];
+                sst_r[0] = sst_r[1];
+                taint[0] = taint[1];
+                frm_r[1] = f0;
+                sst_r[1] = s0;
+                taint[1] = t0;
+                ovf >>= 16;
+            } else {
+                ovf &= 0xffffu;
+            }
+            ck.split_enter(h);
+#if FPLDPC_TAIL_TRACE
+            if (tid == 0) tt_split = __builtin_amdgcn_s_memrealtime();
+#endif
+            __syncthreads();
+            for (;; ++s)
+                if (!step_body(s, std::true_type{})) break;
+        }
+    }
+    if (a.totals && tid == 0) {  // this workgroup's frames (each counter < 2^31 per workgroup)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (misc[kTotW + c]) atomicAdd(&a.totals[c], (unsigned long long)(unsigned)misc[kTotW + c]);
+    }
+    chain_exit(a);
+}
+
+}  // namespace
+}  // namespace fpldpc

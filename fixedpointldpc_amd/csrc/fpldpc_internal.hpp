@@ -88,7 +88,7 @@ struct KernelChoice {
 // [2] frames in fallback list 0, [3] second fallback's work counter, [4] frames in list 1,
 // [5] workgroups out of the call's last kernel, [6] / [7] the last call's list 0 / 1 sizes.
 // Zeroed once at decoder creation; the last workgroup of each call's last kernel resets [0..5]
-// (chain_exit, fpldpc_kernels.hip), so a decode call issues kernels only.
+// (chain_exit, fpldpc_flood_device.hpp), so a decode call issues kernels only.
 constexpr int kCounterInts = 8;
 constexpr int kCountFb0 = 2;
 constexpr int kCountFb1 = 4;
@@ -117,7 +117,7 @@ struct EdgeTables {
     int32_t *c2v = nullptr;
 };
 int edge_kernel_dc(int dc_max);  // 8 / 16 / 32 / 48 / 64, 0 if dc_max > 64
-// One frame on stream: edge [dc_max][m] device edge RAM, in/out (fpldpc_kernels.hip flood_edges).
+// One frame on stream: edge [dc_max][m] device edge RAM, in/out (fpldpc_flood_int32.hpp flood_edges).
 int launch_decode_frame(const LaunchArgs &args, const EdgeTables &t, int32_t *edge, int keep, void *stream);
 
 }  // namespace fpldpc

@@ -49,7 +49,7 @@ constexpr size_t lay_state_bytes(int mode) { return mode == kLaySat16 ? sizeof(i
 __host__ __device__ constexpr size_t lay_post_words(int mode, int n) { return ((size_t)n * lay_state_bytes(mode) + 3) / 4; }
 
 // x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
-// fpldpc_kernels.hip: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
+// fpldpc_flood_device.hpp: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
 __device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
     const int a = x < 0 ? -x : x;
     const int b = y < 0 ? -y : y;

@@ -40,14 +40,31 @@ def test_per_kernel_translation_units():
         assert src in _build.SOURCES, src
         # device-side only (-Xarch_device before each -mllvm=): the host compile stays plain
         assert all(f == "-Xarch_device" for f in flags[0::2]) and all(f.startswith("-mllvm=") for f in flags[1::2])
+    import re
+    a_kernel, w_kernel = "flood_pk<ArrayChecks<47>, 3>", "flood_pk<TableChecks<8, 4, 7, 3>, 4>"
+    # each unit defines its host stubs over its own instantiation, and is a unit of its own: it
+    # includes headers, no other unit's source
     a1 = open(os.path.join(_build.CSRC, "fpldpc_kernels_a1.hip")).read()
-    assert "#define FPLDPC_TU_ARRAY1 1" in a1 and '#include "fpldpc_kernels.hip"' in a1
+    assert "const void *array47_pair_kernel() { return reinterpret_cast<const void *>(&%s); }" % a_kernel in a1
+    assert ("const void *array47_pair_outguard_kernel() { return reinterpret_cast<const void *>"
+            "(&flood_pk<ArrayChecksOutGuard<47>, 3>); }") in a1
+    w1 = open(os.path.join(_build.CSRC, "fpldpc_kernels_w1.hip")).read()
+    assert "const void *table8_pair_kernel() { return reinterpret_cast<const void *>(&%s); }" % w_kernel in w1
+    assert "fpldpc_kernels_w1.hip" in _build.SOURCES and "fpldpc_kernels_w1.hip" in _build.DEVICE_TUS
+    for text in (a1, w1):
+        incs = re.findall(r'^\s*#\s*include\s*[<"]([^>"]+)[>"]', text, re.M)
+        assert incs and not [i for i in incs if not i.endswith((".hpp", ".h"))], incs
+    assert "table8_pair_kernel" not in a1 and "array47_pair" not in w1
+    # the main unit takes the kernels through the stubs and names neither instantiation itself
     main = open(os.path.join(_build.CSRC, "fpldpc_kernels.hip")).read()
     assert "reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_kernel()))" in main
-    w1 = open(os.path.join(_build.CSRC, "fpldpc_kernels_w1.hip")).read()
-    assert "#define FPLDPC_TU_TABLE1 1" in w1 and '#include "fpldpc_kernels.hip"' in w1
-    assert "fpldpc_kernels_w1.hip" in _build.SOURCES and "fpldpc_kernels_w1.hip" in _build.DEVICE_TUS
+    assert "reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_outguard_kernel()))" in main
     assert "reinterpret_cast<KernelFn>(const_cast<void *>(table8_pair_kernel()))" in main
+    code = re.sub(r"//[^\n]*", "", main)  # (its comments may speak of them)
+    assert a_kernel not in code and w_kernel not in code and "flood_pk<ArrayChecksOutGuard<47>" not in code
+    assert not re.search(r'#\s*include\s*"[^"]*\.hip"', main)
+    # no source is compiled twice under a per-unit macro
+    assert not [f for f in os.listdir(_build.CSRC) if "FPLDPC_TU_" in open(os.path.join(_build.CSRC, f)).read()]
     out = __import__("subprocess").run(["nm", "-DC", _build.LIB], capture_output=True, text=True).stdout
     assert "fpldpc::array47_pair_kernel()" in out and "fpldpc::table8_pair_kernel()" in out
 

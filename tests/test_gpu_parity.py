@@ -251,7 +251,7 @@ def test_split_tail_parity(F, O, codes, torch_dev, monkeypatch, cfg, split):
 
 @pytest.mark.parametrize("cfg", ["A", "W", "R"])
 def test_int16_range_fallback(F, O, codes, torch_dev, cfg):
-    """The packed kernels' int16-range guard (fpldpc_kernels.hip flood_pk: |LLR| <= kLlrMax = 8000
+    """The packed kernels' int16-range guard (fpldpc_flood_pk.hpp flood_pk: |LLR| <= kLlrMax = 8000
     and every c2v magnitude below cmax = 2^b - 1) tripped by the c2v-range taint with in-range
     LLRs: frames whose LLRs all have magnitudes 5000..8000 produce c2v above cmax (A 4095, W 2047,
     R 511: the largest 2^b - 1 with 8000 + (dv_max + 1)(2^(b+1) - 1) + 64 <= 32767) in their first

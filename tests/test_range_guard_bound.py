@@ -1,4 +1,4 @@
-"""The packed A kernel's range guard from two chain values (fpldpc_kernels.hip ArrayChecks::kChainGuard).
+"""The packed A kernel's range guard from two chain values (fpldpc_flood_checks_array.hpp ArrayChecks::kChainGuard).
 
 Property: with L = (deg - 1) // 2, F the forward and B the backward chain of the reference's fold,
     max_k |c2v_k| <= max(|F_{L-1}|, |B_{L+1}|) + (L + 1) * C,

@@ -1,4 +1,5 @@
-"""A/B builds of the main kernel translation unit (fpldpc_kernels.hip: R's MixChecks kernel, the
+"""A/B builds of the main kernel translation unit (fpldpc_kernels.hip, which instantiates every kernel
+of the fpldpc_flood_*.hpp headers but A's and the degree-sorted W's: R's MixChecks kernel, the
 fallbacks, the per-frame kernels) under other code-generation options: build/ab/<name>.so."""
 import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fixedpointldpc_amd import _build as b

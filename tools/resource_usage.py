@@ -3,6 +3,10 @@
 kernel-resource-usage, device-only compile for gfx950): the quick check that a kernel change did not
 add spills or drop occupancy, before any GPU run.
 
+The file is a translation unit, by default fpldpc_kernels.hip; the A and W kernels are instantiated in
+fpldpc_kernels_a1.hip and fpldpc_kernels_w1.hip, and the fpldpc_flood_*.hpp headers they all include
+hold templates only.
+
 usage: tools/resource_usage.py [file.hip] [name-filter] [-D...]"""
 import os
 import re

@@ -1,5 +1,5 @@
 // Box-plus chain micro-benchmark (diagnostic only): the packed kernel's bp_mag2 step
-// (3 v_pk_min_u16 + 8 full-rate ops, as in fpldpc_kernels.hip) iterated in C independent chains
+// (3 v_pk_min_u16 + 8 full-rate ops, as in fpldpc_flood_packed.hpp's bp_mag2) iterated in C independent chains
 // per lane, WPS waves per SIMD on every CU; reports shader cycles (s_memtime) per VALU
 // instruction per SIMD.  Compared with the v_add / v_pk_min rates of dep_latency.hip it shows
 // what the decoder's own instruction mix can issue at.
