@@ -27,6 +27,8 @@ SOURCES = [
     "fpldpc_layered_minsum.hip",
     # the flooding min-sum decoder: as the layered units, outside the build id
     "fpldpc_minsum.hip",
+    # the global form of the two min-sum decoders (codes whose state does not fit LDS): outside the build id too
+    "fpldpc_minsum_global.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -166,12 +166,16 @@ int fpldpc_layered_describe(fpldpc_layered_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
     const int w = snprintf(buf, cap, "%s L=%d layers=%d grid=%d threads=%d lds=%zu device=%d", dec->lc.name, dec->L,
                            dec->layers, dec->lc.grid, dec->lc.threads, dec->lc.lds_bytes, dec->device);
-    if (dec->lc.mode == kLayMinsum && w > 0 && (size_t)w < cap)
-        snprintf(buf + w, cap - w, " sat=%d/%d ms=%d/16-%d state=compressed", dec->post_bits, dec->msg_bits, dec->scale_16,
-                 dec->offset);
-    else if (dec->lc.mode != kLayUnsat && w > 0 && (size_t)w < cap)
+    if (dec->lc.mode == kLayMinsum && w > 0 && (size_t)w < cap) {
+        const int w2 = snprintf(buf + w, cap - w, " sat=%d/%d ms=%d/16-%d state=compressed", dec->post_bits, dec->msg_bits,
+                                dec->scale_16, dec->offset);
+        // the global form: the bytes of its scratch
+        if (!dec->lc.lds_state && w2 > 0 && (size_t)(w + w2) < cap)
+            snprintf(buf + w + w2, cap - w - w2, " scratch=%zu", dec->lc.scratch_bytes);
+    } else if (dec->lc.mode != kLayUnsat && w > 0 && (size_t)w < cap) {
         snprintf(buf + w, cap - w, " sat=%d/%d state=%s", dec->post_bits, dec->msg_bits,
                  dec->lc.mode == kLaySat16 ? "i16" : "i32");
+    }
     return FPLDPC_OK;
 }
 
@@ -325,8 +329,11 @@ int fpldpc_minsum_destroy(fpldpc_minsum_t dec) {
 int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
     const fpldpc_layered *d = dec->lay;
-    snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d ms=%d/16-%d state=compressed", d->lc.name,
-             d->lc.grid, d->lc.threads, d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits, d->scale_16, d->offset);
+    const int w = snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d ms=%d/16-%d state=compressed",
+                           d->lc.name, d->lc.grid, d->lc.threads, d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits,
+                           d->scale_16, d->offset);
+    // the global form: the bytes of its scratch
+    if (!d->lc.lds_state && w > 0 && (size_t)w < cap) snprintf(buf + w, cap - w, " scratch=%zu", d->lc.scratch_bytes);
     return FPLDPC_OK;
 }
 

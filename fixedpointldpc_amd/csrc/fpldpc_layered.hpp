@@ -1,7 +1,8 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
 // (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* and fpldpc_minsum_* C ABI), fpldpc_layered.hip,
-// fpldpc_layered_minsum.hip and fpldpc_minsum.hip (kernels; through fpldpc_layered_device.hpp, beside which
-// fpldpc_layered_host.hpp holds their shared choice and launch steps and fpldpc_minsum_device.hpp the min-sum rule).
+// fpldpc_layered_minsum.hip, fpldpc_minsum.hip and fpldpc_minsum_global.hip (kernels; through
+// fpldpc_layered_device.hpp, beside which fpldpc_layered_host.hpp holds their shared choice and launch steps and
+// fpldpc_minsum_device.hpp the min-sum rule).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
 // c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding
@@ -29,14 +30,14 @@ enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3, kFloodMinsum
 struct LayeredChoice {
     int mode = kLayUnsat;
     int dc = 0;              // kernel DC: 8 / 16 / 32 / 48 / 64 >= dc_max, or the exact degree (47)
-    bool lds_state = false;  // c2v (and the index table) in LDS; else per-workgroup global scratch
+    bool lds_state = false;  // c2v / check state (and the index table) in LDS; else per-workgroup global scratch
     bool computed = false;   // forward array code: v = k*p + (j + i*k) mod p, no index table
     bool table_lds = false;  // the index table is staged in LDS (with lds_state, table codes)
     bool exact = false;      // every check has degree dc: straight-line slot loops, no degree table
     int threads = 64;
     int grid = 0;            // resident workgroups (persistent)
     size_t lds_bytes = 0;
-    size_t scratch_bytes = 0; // global c2v: grid * dc_max * m entries of the state type
+    size_t scratch_bytes = 0; // global c2v: grid * dc_max * m entries of the state type; min-sum: grid * slice
     char name[96] = "";
 };
 
@@ -65,18 +66,25 @@ struct LayeredArgs {
     int k_info = 0;
     int sat_msg = 0;                 // S_m
     int *counters = nullptr;         // kLayeredCounterInts
-    void *c2v_scratch = nullptr;     // [grid][dc_max][m] of the state type when !lds_state
+    void *c2v_scratch = nullptr;     // [grid][dc_max][m] of the state type when !lds_state (min-sum: [grid] slices)
 };
 
 // Envelope and kernel choice for (code, L, mode) on `device`; FPLDPC_ERR_UNSUPPORTED outside the envelope.
 int layered_choose(const fpldpc_code &code, int L, int device, int mode, LayeredChoice *out);
 int layered_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
-// The same pair for the min-sum decoder (mode kLayMinsum; lds_state is always true, there is no scratch).
+// The same pair for the min-sum decoder (mode kLayMinsum; lds_state: the check state in LDS, no scratch).
 int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out);
 int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
-// The same pair for the flooding min-sum decoder (mode kFloodMinsum, fpldpc_minsum.hip): no layers, no scratch.
+// The same pair for the flooding min-sum decoder (mode kFloodMinsum, fpldpc_minsum.hip): no layers.
 int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out);
 int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// The global form of the two min-sum decoders (fpldpc_minsum_global.hip; !lds_state), which the two pairs
+// above delegate to where the LDS form does not fit or the environment variable `env` is "global".
+// minsum_global_choose completes a choice whose mode, dc, exact and threads are set: the check state (and
+// the flooding accumulators) in scratch_bytes = grid * slice of global memory, passed as c2v_scratch.
+bool minsum_state_forced_global(const char *env);
+int minsum_global_choose(const fpldpc_code &code, int device, LayeredChoice *lc);
+int minsum_global_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
 // Raises a kernel's dynamic-LDS limit on the current device, never lowers it (fpldpc_layered.hip).
 hipError_t raise_dynamic_lds(const void *fn, size_t bytes);
 

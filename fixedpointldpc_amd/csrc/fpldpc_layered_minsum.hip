@@ -8,7 +8,9 @@
 // fpldpc_minsum_device.hpp defines it; with its t[k] and new[k] a layer does
 //     post[v_k] = clamp(t[k] + new[k], S_p)
 // One state entry per check in LDS, lane j of a layer on entry l*L + j (one 16-byte access per lane,
-// consecutive lanes on consecutive entries).  There is no per-edge c2v array and no global scratch for any code.
+// consecutive lanes on consecutive entries).  There is no per-edge c2v array for any code and, in the kernel
+// of this unit, no global scratch: a code whose state does not fit LDS takes layered_minsum_global
+// (fpldpc_minsum_global.hip), which layered_minsum_choose / layered_minsum_launch below delegate to.
 //
 // A check is a gather and two passes over its slots.  The gather issues every post[v_k] read before any
 // is waited for and keeps v_k (uint16) and the posterior packed in one register per slot.  Pass 1 rebuilds
@@ -124,24 +126,27 @@ MinsumFn minsum_fn(const LayeredChoice &lc) {
 
 }  // namespace
 
-// Envelope: check degrees 2..64, any valid layer size, and the int16 posteriors, the control words, 16
-// bytes per check and one byte per check of the degree table (unless the kernel's DC is every check's
-// degree) within the CU's 160 KiB of LDS.  The index table is placed as in layered_choose
-// (FPLDPC_LAYERED_TABLE=global / lds places it regardless).
+// Envelope: check degrees 2..64, any valid layer size and n <= 65535.  The kernels of this unit where the
+// int16 posteriors, the control words, 16 bytes per check and one byte per check of the degree table
+// (unless the kernel's DC is every check's degree) fit the CU's 160 KiB of LDS; there the index table is
+// placed as in layered_choose (FPLDPC_LAYERED_TABLE=global / lds places it regardless).  Every other code,
+// and every code under FPLDPC_LAYERED_MINSUM_STATE=global, takes the global form (fpldpc_minsum_global.hip).
 int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out) {
     LayeredChoice lc;
     if (int st = lay_choice_of_code(code, kLayMinsum, "layered", &lc)) return st;
     lc.threads = std::min(kLayMaxNT, (L + 63) / 64 * 64);
     const size_t base = ms_state_offset(code.n) + kMsStateBytes * code.m + (lc.exact ? 0 : (size_t)code.m);
-    if (base > kLdsMax)
-        return fail(FPLDPC_ERR_UNSUPPORTED, "layered min-sum decoder: posteriors and check state do not fit 160 KiB of LDS");
-    if (int st = lay_choose_lds(minsum_fn(lc), code, base, "FPLDPC_LAYERED_TABLE", device, "layered min-sum", "layered_minsum", &lc))
+    if (base > kLdsMax || minsum_state_forced_global("FPLDPC_LAYERED_MINSUM_STATE")) {
+        if (int st = minsum_global_choose(code, device, &lc)) return st;
+    } else if (int st = lay_choose_lds(minsum_fn(lc), code, base, "FPLDPC_LAYERED_TABLE", device, "layered min-sum", "layered_minsum", &lc)) {
         return st;
+    }
     *out = lc;
     return FPLDPC_OK;
 }
 
 int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream) {
+    if (!lc.lds_state) return minsum_global_launch(lc, args, scale_16, offset, stream);
     return lay_launch(minsum_fn(lc), lc, args, MinsumArgs{args, scale_16, offset}, stream, "layered min-sum");
 }
 

@@ -14,7 +14,9 @@
 // for step t + 1: nobody else touches it in this step.  Then one barrier, the syndrome on `nxt` (a second
 // barrier), and the buffers rotate.  |L + sum| <= S_p + dv_max * S_m < 2^31: int32 is always enough.
 // A check is the gather and the two passes of layered_minsum; pass 2 issues the atomics where the layered
-// kernel stores posteriors.  There is no per-edge state, no per-variable pass and no global scratch.
+// kernel stores posteriors.  There is no per-edge state, no per-variable pass and, in the kernels of this
+// unit, no global scratch: a code whose state does not fit LDS takes flood_minsum_global
+// (fpldpc_minsum_global.hip), which flood_minsum_choose / flood_minsum_launch below delegate to.
 #include "fpldpc_layered_host.hpp"
 #include "fpldpc_minsum_device.hpp"
 
@@ -139,24 +141,28 @@ FloodMsFn flood_fn(const LayeredChoice &lc) {
 
 }  // namespace
 
-// Envelope: check degrees 2..64, and the check state, three int32 accumulators, the int16 LLRs, the control
-// words and one byte per check of the degree table (unless the kernel's DC is every check's degree) within
-// the CU's 160 KiB of LDS.  The index table is placed as in the layered decoders, under a switch of its own
-// (FPLDPC_MINSUM_TABLE=global / lds places it regardless).
+// Envelope: check degrees 2..64 and n <= 65535.  The kernels of this unit where the check state, three int32
+// accumulators, the int16 LLRs, the control words and one byte per check of the degree table (unless the
+// kernel's DC is every check's degree) fit the CU's 160 KiB of LDS; there the index table is placed as in
+// the layered decoders, under a switch of its own (FPLDPC_MINSUM_TABLE=global / lds places it regardless).
+// Every other code, and every code under FPLDPC_MINSUM_STATE=global, takes the global form
+// (fpldpc_minsum_global.hip).
 int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out) {
     LayeredChoice lc;
     if (int st = lay_choice_of_code(code, kFloodMinsum, "flooding min-sum", &lc)) return st;
     lc.threads = std::min(kLayMaxNT, (code.m + 63) / 64 * 64);
     const size_t base = fm_table_offset(code.n, code.m) + (lc.exact ? 0 : (size_t)code.m);
-    if (base > kLdsMax || code.n > 65535)
-        return fail(FPLDPC_ERR_UNSUPPORTED, "flooding min-sum decoder: accumulators and check state do not fit 160 KiB of LDS");
-    if (int st = lay_choose_lds(flood_fn(lc), code, base, "FPLDPC_MINSUM_TABLE", device, "flooding min-sum", "flood_minsum", &lc))
+    if (base > kLdsMax || code.n > 65535 || minsum_state_forced_global("FPLDPC_MINSUM_STATE")) {
+        if (int st = minsum_global_choose(code, device, &lc)) return st;
+    } else if (int st = lay_choose_lds(flood_fn(lc), code, base, "FPLDPC_MINSUM_TABLE", device, "flooding min-sum", "flood_minsum", &lc)) {
         return st;
+    }
     *out = lc;
     return FPLDPC_OK;
 }
 
 int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream) {
+    if (!lc.lds_state) return minsum_global_launch(lc, args, scale_16, offset, stream);
     return lay_launch(flood_fn(lc), lc, args, MinsumArgs{args, scale_16, offset}, stream, "flooding min-sum");
 }
 

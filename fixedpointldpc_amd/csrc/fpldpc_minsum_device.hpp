@@ -1,6 +1,7 @@
 // fpldpc_minsum_device.hpp -- the min-sum check rule with compressed check state, defined once for the two
-// kernels that run it (fpldpc_layered_minsum.hip: layered schedule; fpldpc_minsum.hip: flooding schedule).
-// Included by those two translation units only.
+// kernels that run it (fpldpc_layered_minsum.hip: layered schedule; fpldpc_minsum.hip: flooding schedule) and
+// their forms with the state in global memory (fpldpc_minsum_global.hip).  Included by those three
+// translation units only.
 //
 // Normalised / offset min-sum: with f(x) = max(((x * scale_16) >> 4) - offset, 0), for a check c with
 // slots k on variables v_k,

@@ -248,11 +248,19 @@ int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, i
  * S_p > S_m keeps the sign of a pinned posterior minus its own message; the on-chip state is int16.
  * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
  * use them.  On chip a check keeps 16 bytes whatever its degree -- f(m1), f(m2), k1 and a 64-bit sign
- * word, from which every c2v[c][k] is rebuilt -- so there is no per-edge state and no global scratch.
- * Check degrees 2..64; any code whose int16 posteriors and 16 (17 with mixed degrees) bytes per check fit 160 KiB.
+ * word, from which every c2v[c][k] is rebuilt -- so there is no per-edge state.
+ * Envelope: check degrees 2..64, a valid layering and n <= 65535 (every code the loader accepts); no code is
+ * refused for its size.  Placement of the check state: in LDS wherever the int16 posteriors, the control
+ * words and 16 (17 with mixed degrees) bytes per check, 2 n + 17 m + 16 bytes at most, fit the CU's 160 KiB,
+ * with no global scratch; otherwise "global": LDS keeps the posteriors, the control words and (where they
+ * fit) the degrees, and each resident workgroup keeps its frame's state [m] x 16 bytes in a slice of
+ * roundup(16 m, 256) bytes of a scratch of grid * slice bytes that the decoder owns.  The environment variable
+ * FPLDPC_LAYERED_MINSUM_STATE=global, read at creation, chooses the global placement for a code that fits
+ * (a diagnostic switch; any other value is ignored).  Results do not depend on the placement.
  * The object is an fpldpc_layered_t like any other: destroy, set_reference, decode and decode_host apply
- * unchanged; describe names the kernel layered_minsum<..> and ends with
- * " sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed". */
+ * unchanged; describe names the kernel layered_minsum<..> (with ",mem=global" inside the brackets in the
+ * global placement) and ends with " sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed",
+ * followed by " scratch=<bytes>" in the global placement. */
 int fpldpc_layered_create_minsum(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks,
                                  int32_t post_bits, int32_t msg_bits, int32_t scale_16, int32_t offset,
                                  fpldpc_layered_t *out);
@@ -297,17 +305,24 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
  * FPLDPC_ERR_ARG (with a message, tested before a HIP device is looked for) unless
  *     2 <= msg_bits < post_bits <= 16,   1 <= scale_16 <= 16,   0 <= offset <= S_m.
  * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
- * use them.  On chip a check keeps 16 bytes whatever its degree, as in the layered min-sum decoder; there is
- * no per-edge state and no global scratch for any code.  Envelope: check degrees 2..64 and 14 n + 17 m + 32
- * bytes (three int32 accumulators, the int16 LLRs, the state and the degrees; the index table joins them only
- * where it fits) within the CU's 160 KiB of LDS; outside it FPLDPC_ERR_UNSUPPORTED (with a message).
+ * use them.  A check keeps 16 bytes whatever its degree, as in the layered min-sum decoder; there is no
+ * per-edge state.  Envelope: check degrees 2..64 and n <= 65535 (every code the loader accepts); outside it
+ * FPLDPC_ERR_UNSUPPORTED (with a message); no code is refused for its size.  Placement of the state: in LDS
+ * wherever 14 n + 17 m + 32 bytes (three int32 accumulators, the int16 LLRs, the state and the degrees; the
+ * index table joins them only where it fits) fit the CU's 160 KiB, with no global scratch; otherwise
+ * "global": LDS keeps the int16 LLRs, the control words and (where they fit) the degrees, and each resident
+ * workgroup keeps its frame's state [m] x 16 bytes and accumulators [3][n] int32 in a slice of
+ * roundup(16 m + 12 n, 256) bytes of a scratch of grid * slice bytes that the decoder owns.  The environment
+ * variable FPLDPC_MINSUM_STATE=global, read at creation, chooses the global placement for a code that fits
+ * (a diagnostic switch; any other value is ignored).  Results do not depend on the placement.
  * FPLDPC_ERR_HIP without a HIP device. */
 typedef struct fpldpc_minsum *fpldpc_minsum_t;
 int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
                          int32_t scale_16, int32_t offset, fpldpc_minsum_t *out);
 int fpldpc_minsum_destroy(fpldpc_minsum_t dec);
 /* "flood_minsum<DC=..,addr=computed|table|gtable,deg=exact|table> grid=N threads=N lds=N device=N
- * sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed". */
+ * sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed"; in the global placement
+ * "flood_minsum<DC=..,addr=gtable,deg=exact|table,mem=global> ... state=compressed scratch=<bytes>". */
 int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap);
 /* As fpldpc_set_reference. */
 int fpldpc_minsum_set_reference(fpldpc_minsum_t dec, const int32_t *info_index, const uint8_t *info_bits, int32_t k);
