@@ -137,6 +137,7 @@ def lib():
         "fpldpc_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult), P]),
         "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
         "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
+        "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("FPLDPC_LIB_PATH") and not hasattr(L, name):
@@ -166,6 +167,7 @@ EXPORTED = [
     "fpldpc_minsum_decode", "fpldpc_minsum_decode_host",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
+    "fpldpc_testing_stationary_exits",  # include/fpldpc_testing.h: the last call's stationary exits
 ]
 
 
@@ -283,6 +285,12 @@ class Decoder:
         c = np.zeros(2, np.int32)
         _check(lib().fpldpc_decoder_fallback_counts(self._h, _ptr(c)))
         return int(c[0]), int(c[1])
+
+    def stationary_exits(self):
+        """Frames the last completed decode call ended by the stationary exit (include/fpldpc_testing.h)."""
+        c = ctypes.c_int32(0)
+        _check(lib().fpldpc_testing_stationary_exits(self._h, ctypes.byref(c)))
+        return c.value
 
     def set_reference(self, info_index, info_bits):
         idx = np.ascontiguousarray(info_index, np.int32)

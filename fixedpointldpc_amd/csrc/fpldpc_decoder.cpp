@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fpldpc_internal.hpp"
+#include "fpldpc_testing.h"
 
 using namespace fpldpc;
 
@@ -190,6 +191,7 @@ int create_decoder(const fpldpc_code *code, const fpldpc_params *params, const K
     d->dcode.cdeg = d->d_cdeg;
     // Diagnostics, read once here rather than on every decode call (see fpldpc_decode)
     if (const char *sp = getenv("FPLDPC_SPLIT_TAIL")) d->split_tail = *sp != '0';
+    if (const char *se = getenv("FPLDPC_STATIONARY_EXIT")) d->stationary_exit = *se != '0';
     if (diag) {
         const char *probe_env = getenv("FPLDPC_CLOCK_PROBE");
         d->diag_probe = probe_env && *probe_env == '1';
@@ -243,7 +245,21 @@ int fpldpc_decoder_fallback_counts(fpldpc_decoder_t dec, int32_t counts[2]) {
     int32_t c[kCounterInts];
     HIP_TRY(hipMemcpy(c, dec->d_counter, sizeof c, hipMemcpyDeviceToHost));
     counts[0] = c[kCountFb0Last];
-    counts[1] = c[kCountFb1Last];
+    counts[1] = dec->kc.fallback2 == Variant::kNone ? 0 : c[kCountFb1Last];  // (no list 1: the stationary exits' word)
+    return FPLDPC_OK;
+}
+
+// Test-only (include/fpldpc_testing.h): frames the last completed decode call ended by the stationary exit.
+int fpldpc_testing_stationary_exits(void *decoder, int32_t *count) {
+    fpldpc_decoder_t dec = static_cast<fpldpc_decoder_t>(decoder);
+    if (!dec || !count) return fail(FPLDPC_ERR_ARG, "null argument");
+    *count = 0;
+    if (dec->kc.fallback == Variant::kNone || dec->kc.fallback2 != Variant::kNone) return FPLDPC_OK;
+    DeviceGuard g(dec->device);
+    HIP_TRY(hipEventSynchronize(dec->last_done));
+    int32_t c[kCounterInts];
+    HIP_TRY(hipMemcpy(c, dec->d_counter, sizeof c, hipMemcpyDeviceToHost));
+    *count = c[kCountFb1Last];
     return FPLDPC_OK;
 }
 
@@ -319,6 +335,7 @@ int fpldpc_decode(fpldpc_decoder_t dec, const void *llr, int32_t llr_type, int32
     a.c2v_scratch = dec->d_scratch;
     a.bfe_w = (uint32_t)std::max(0, __builtin_popcount((unsigned)a.mask) - 2);
     a.split_tail = dec->split_tail ? 1 : 0;
+    a.stationary_exit = dec->stationary_exit ? 1 : 0;
     if (dec->kc.fallback != Variant::kNone) {
         if (batch > dec->fb_cap) {  // grows to the largest batch seen (not inside graph capture)
             (void)hipFree(dec->d_fb_list);

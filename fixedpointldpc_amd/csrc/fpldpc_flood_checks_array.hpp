@@ -43,6 +43,7 @@ struct ArrayChecks {
     uint32_t offs[kOW];  // kStoreOffs: slot 2w's byte offset in bits 0-15, slot 2w+1's in bits 16-31
     uint32_t tabq[kLdsOffs ? CPL : 1];  // kLdsOffs: LDS byte address of check q's table row
     bool act[CPL];
+    uint32_t pxp;  // kStationary: the XOR of the check's posterior words at the step before (the exit's trigger)
     // LDS byte address of stored-offset slot k in the buffer at base
     __device__ __forceinline__ uint32_t soff(int k, uint32_t base) const {
         return lds_at<kSdwa>(offs[kStoreOffs ? k >> 1 : 0], k & 1, base);
@@ -76,6 +77,7 @@ struct ArrayChecks {
         for (int q = 0; q < CPL; ++q) {
             const int c = tid + q * NT;  // this lane's checks
             act[q] = c < a.m;
+            if (kStationary) pxp = 0;
             row[q] = act[q] ? (uint32_t)(c / P) : 0u;
             col[q] = act[q] ? (uint32_t)(c % P) : 0u;
 #pragma unroll
@@ -96,7 +98,9 @@ struct ArrayChecks {
     // One flooding step for this lane's checks: gather from buffer pc, update, scatter-add into
     // buffer pn (LDS byte addresses).  par: bit 15 / 31 = OR over the lane's checks
     // of each check's syndrome parity for the low / high frame; ovor |= every c2v magnitude, or
-    // (kChainGuard) a bound on them all.
+    // (kChainGuard) a bound on them all.  kStationary: par's other bits are non-zero in a half when the
+    // XOR of the check's posterior words differs, below the sign, from the step before's -- the
+    // stationary exit's trigger, a hash: unchanged posteriors leave it zero.
     //
     // The chain guard.  bp_mag(a, b) <= min(a, b) + C (packed_cmax), so along the fold
     //   F_j <= F_{j-1} + C,  B_j <= B_{j+1} + C,  c2v_k = F_{k-1} [+] B_{k+1} <= min(F_{k-1}, B_{k+1}) + C,
@@ -119,6 +123,7 @@ struct ArrayChecks {
     __device__ __forceinline__ void step_g(const KArgs &a, const uint32_t *, uint32_t *, uint32_t pc, uint32_t pn, u16x2 C2,
                                            uint32_t M2, uint32_t &par, uint32_t &ovor) {
         uint32_t fail = 0;  // OR over the lane's checks of each check's parity (not their XOR)
+        [[maybe_unused]] uint32_t trig = 0;
         // (literal operands: the same mask constants in VGPRs measured the same, profiles/r2/ab/bp_form.txt)
         constexpr uint32_t SGN = 0x80008000u, MAG = 0x7fff7fffu;
 #pragma unroll
@@ -283,6 +288,10 @@ struct ArrayChecks {
             }
             // parity of the hard bits = parity of the NOT-hard bits, inverted for an odd degree
             fail |= (px ^ ((P & 1) ? 0x80008000u : 0u)) & 0x80008000u;
+            if constexpr (kStationary) {
+                trig = (px ^ pxp) & 0x7fff7fffu;
+                pxp = px;
+            }
             // Middle-out schedule of the reference's fold (:83-116): the forward chain F and the
             // backward chain B run side by side (two independent dependency chains per lane):
             // phase 1 builds F_0..F_{L-1} and B_{L+1}..B_{P-1}; phase 2 extends F rightwards and B
@@ -371,6 +380,7 @@ struct ArrayChecks {
             }
         }
         par = fail;
+        if constexpr (kStationary) par |= trig;
     }
     // Syndrome of buffer pc only (no update): bits 15 / 31 of par as in step().  The c2v state is
     // left as it is; every frame in flight ends at this step and is refilled (state cleared) or idle.
@@ -414,6 +424,53 @@ struct ArrayChecks {
                 if (finished & 1) st[q][k] -= (uint32_t)carry_lo(st[q][k]);
                 if (finished & 2) st[q][k] = (uint32_t)carry_lo(st[q][k]);
             }
+    }
+
+    // ---- The stationary exit's verification (flood_pk, DESIGN.md "Stationary exit (round 15)") ----
+    // After a step the state st[0][k] is the c2v of the update just made.  stat_verify leaves it in this
+    // workgroup's slice of global scratch ([P][NT] words: slot k of every lane is one coalesced row) and,
+    // with `compare` (wave-uniform), first reads what the call of the step before left there.  It
+    // returns the OR over the slots of old ^ new, both with the carry form's borrow undone (x + 2 (x &
+    // 0x8000): the high half alone), so bits 0-15 / 16-31 are zero iff every c2v of the lane's check in
+    // the low / high frame is what it was one update earlier.  In the split form (one frame, state word
+    // j the pair c2v_j, c2v_{P-1-j}) the same over SLOTS = SL + 1 words, and any set bit is a change.
+    // One instruction stream with a branch round each batch's loads: as two instantiations hipcc merged
+    // the arms' common prefix, all P borrow terms at once, and the kernel spilled.  The slice address (the
+    // caller's) and the lane index are opaque, or the P / G row addresses are hoisted out of the step
+    // loop and held in registers across the check step; the scheduling barriers keep the unit's max-ILP
+    // scheduler from issuing every load first, and the change word is pinned after each batch, or its
+    // XORs sink to the end and every old and new word stays live till then.
+    static constexpr bool kStationary = CPL == 1 && kStoreOffs;
+    static constexpr int kStatWords = P * NT;  // scratch words per workgroup
+    static constexpr int kStatSlots = P;       // state words compared in the packed form
+    static constexpr int kStatSplitSlots = (P - 1) / 2 + 1;  // in the split form (the pairs S[0..SL])
+    template <int SLOTS>
+    __device__ __forceinline__ uint32_t stat_verify(uint32_t *slice, int tid, bool compare) const {
+        uint32_t chg = 0;
+        constexpr int G = 4;  // loads in flight per lane
+        asm volatile("" : "+v"(tid));
+#pragma unroll
+        for (int k0 = 0; k0 < SLOTS; k0 += G) {
+            uint32_t *const p = slice + k0 * NT;
+            uint32_t old[G] = {};
+            if (compare) {
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    if (k0 + g < SLOTS) old[g] = p[g * NT + tid];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int k = k0 + g;
+                if (k >= SLOTS) break;
+                const uint32_t x = st[0][k], nw = x + ((x & 0x8000u) << 1);
+                chg |= old[g] ^ nw;
+                p[g * NT + tid] = nw;
+            }
+            asm volatile("" : "+v"(chg));  // (this batch's words are dead from here on)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        return compare ? chg : 0u;
     }
 
     // ---- The tail: one frame, its check split over the lane's two halves (flood_pk) ----
@@ -499,6 +556,10 @@ struct ArrayChecks {
         Sg ^= rot16(Sg) ^ S[L];
         px ^= rot16(px) ^ VL;
         par = (px ^ ((P & 1) ? 0x80008000u : 0u)) & 0x8000u;
+        if constexpr (kStationary) {  // the trigger, as in step_g (the whole check's XOR is in both halves)
+            par |= (px ^ pxp) & 0x7fffu;
+            pxp = px;
+        }
         // phase 1: each half's chain over its own slots
         uint32_t X[L];
         X[0] = S[0] & MAG;
@@ -706,6 +767,7 @@ struct SplitCore {
 template <int P, int NT = 768>
 struct MixChecks {
     static constexpr bool kSplit = false;
+    static constexpr bool kStationary = false;
     static constexpr int kRefillBatch = 0;
     using Reg = ArrayChecks<P, 2, NT, true, true>;
     using Sp = SplitCore<P>;

@@ -38,6 +38,7 @@ struct TableChecks {
     static constexpr bool kSplit = CPL == 4 && QLO == 3 && DC == DMIN + 1;
     static __device__ __forceinline__ uint32_t rot16(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 16); }
     static constexpr int kRefillBatch = 4;
+    static constexpr bool kStationary = false;  // (flood_pk's stationary exit: the A policy's only)
     static constexpr int kTabWords = 0;
     static constexpr int kN = 0;  // code length at run time
     // posteriors as biased pairs with the array policy's borrow-chain sign/magnitude (W +1.0 % over

@@ -55,7 +55,8 @@ struct KArgs {
     int k_info;
     const uint32_t *info_mask;  // [2][hard_words] packed: info positions, reference bits (distinct indices) or null
     int *work_counter;
-    int32_t *c2v_scratch;
+    int32_t *c2v_scratch;  // global-state kernels: [grid][dc][m_pad]; the A kernel: [grid][47][256] words for the
+                           // stationary exit's verification, null = exit off (flood_pk)
     uint32_t bfe_w;  // width_mask = 2^(bfe_w + 2) - 1 (contiguous-mask kernels only)
     // frame-list mode (fallback pass): work item i decodes frame frame_list[i], i < *frame_count
     const int *frame_list;

@@ -53,6 +53,29 @@ __device__ __forceinline__ void split_step_of(CK &ck, const uint32_t *pcp, uint3
     if constexpr (CK::kSplit) ck.split_step(pcp, pnp, pc, pn, C2, M2, par, ovor);
 }
 
+// flood_pk's stationary-exit control words (wave-uniform), for the policies that have the exit
+template <bool ON>
+struct StatCtl {};
+template <>
+struct StatCtl<true> {
+    int stat, sexit;  // a step's decisions: halves verified stationary / ending by that alone
+    int vsk;          // (across set_quick at a refill: the on-bits, and the other half's state << 16)
+    // The exit's state between steps rides in flood_pk's q_live word, which the step loop holds in a
+    // register anyway (every SGPR more that lives across the check step costs spills in it):
+    //   bits 0-1   the live halves, whose fail flags the quick exit wants set (as without the exit)
+    //   bits 2-3   the same halves' `changed` flags, wanted too -- set only while the exit is on
+    //   bits 16-19 the verification state vs, two bits per half (1: the coming step stores, 2: it
+    //              compares); no flag word has these bits, so the quick exit is not taken meanwhile
+    // A flag word (misc[6..8]) only ever carries bits 0-5: fail (0, 1), changed (2, 3), the compare's
+    // result (4, 5).  Bits 16-19 of q_live must stay outside that set (kFlagBits), and both loops read
+    // the state through on() / vs() only.
+    static constexpr int kFlagBits = 0x3f;
+    static_assert((kFlagBits & 0xf0000) == 0, "the verification state must lie outside the flag bits");
+    static __device__ __forceinline__ int word(int live, bool on, int vs) { return live * (on ? 5 : 1) | vs << 16; }
+    static __device__ __forceinline__ bool on(int q_live) { return (q_live & 0xc) != 0; }
+    static __device__ __forceinline__ int vs(int q_live) { return q_live >> 16; }
+};
+
 template <class CK, int WAVES, int NT = kNT>
 __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -62,7 +85,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
     int *const misc = smem + 4 * n;
     // misc: [0,1] frame of half h (-1 idle)  [2,3] start step  [4,5] load taint  [6..8] flag words
     //       [12] final-pass syndrome word  [13] deferred range-check word
-    //       [9,10] bit-error accumulators
+    //       [9,10] bit-error accumulators  [14] frames this workgroup ended by the stationary exit
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u16x2 C2 = (u16x2)(unsigned short)a.C;
     uint32_t M2 = ((1u << a.bfe_w) - 1u) * 0x10001u;
@@ -346,6 +369,22 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
     // steps (A +2.1 %, A @ 4.5 dB +3.1 %, W +2.8 %, W @ 2 dB +2.0 %, R +1.4 %,
     // profiles/r6/ab/quick_exit.txt).  q_live: the live halves (bit h), whose fail flags must be set.
     int q_live = 0, q_until = 0;
+    // The stationary exit (CK::kStationary, DESIGN.md "Stationary exit (round 15)"): a frame whose c2v
+    // messages are the same after two consecutive updates has reached a fixed point of the iteration --
+    // every later update reproduces them, the posteriors and the syndrome -- so it ends there, reported
+    // with max_iter iterations and the outputs max_iter updates give.  Per half:
+    //   trigger  the check step's XOR over each check's posterior words (it has it for the syndrome) is
+    //            what it was at the step before in every lane (flag bits 2 / 3: the hash of half 0 / 1
+    //            changed somewhere); equal posteriors give equal hashes, and neither proves anything
+    //            about the messages: the trigger only arms
+    //   verify   the two steps after it run ck.stat_verify after the check step: the first stores the
+    //            c2v words, the second compares (flag bits 4 / 5: some c2v of the half changed)
+    //   end      no change: the half ends through the end-of-frame path below
+    // On when the launch passes a scratch slice per workgroup (a.c2v_scratch; FPLDPC_STATIONARY_EXIT=0
+    // passes none).  With this policy q_live carries the exit's state too (StatCtl); it is still zero
+    // only when both halves are idle.
+    // (StatCtl is empty for the other policies: their kernels carry no trace of it)
+    [[maybe_unused]] StatCtl<CK::kStationary> sc;
     auto set_quick = [&]() {
         q_live = (frm(0) >= 0 ? 1 : 0) | (frm(1) >= 0 ? 2 : 0);
         q_until = 0x7fffffff;
@@ -353,6 +392,53 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             if (frm(h) >= 0) q_until = min(q_until, sst(h) + a.max_iter - 1);
     };
     set_quick();
+    if constexpr (CK::kStationary) q_live = sc.word(q_live, a.c2v_scratch != nullptr, 0);
+    // The stationary exit's decisions after the barrier of step s, per live half; d = its completed
+    // updates in pc.  A compare that found no change: the update this step made (d + 1 <= max_iter, one
+    // the reference makes) reproduced the c2v of update d, so pn = pc and every later posterior equals
+    // pc -- the half ends on pc (sc.stat).  Armed when the posterior hashes of updates d - 1 and d are
+    // equal (d >= 1: at d = 0 the hash before was another frame's) and the compare, two steps on, still
+    // comes before the last update of either half (s + 2 <= q_until, the smaller of the halves' bounds and
+    // a value the loop holds anyway: the half's own a.max_iter bound cost five more SGPR spills).
+    [[maybe_unused]] auto stat_decide = [&](uint32_t flags, int s) {
+        if constexpr (CK::kStationary) {
+            sc.stat = 0;
+            sc.sexit = 0;
+            if (!sc.on(q_live)) return;
+            int vs = sc.vs(q_live);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (frm(h) < 0) continue;
+                const int d = s - sst(h);
+                int st = vs >> (2 * h) & 3;
+                if (st == 2) {
+                    if (!(flags >> (4 + h) & 1u)) sc.stat |= 1 << h;
+                    st = 0;
+                } else if (st == 1) {
+                    st = 2;
+                }
+                if (st == 0 && !(sc.stat >> h & 1) && !(flags >> (2 + h) & 1u) && d >= 1 && s + 2 <= q_until) st = 1;
+                vs = (vs & ~(3 << (2 * h))) | st << (2 * h);
+            }
+            q_live = (q_live & 0xffff) | vs << 16;
+        }
+    };
+    // the verification of the step just made, while one is pending: the c2v words (the packed state's
+    // P, the split form's SL + 1) against the step before's, or stored for the next; flag bits 4 / 5
+    [[maybe_unused]] auto stat_check = [&](auto words_c, int s) {
+        if constexpr (CK::kStationary) {
+            if (!sc.vs(q_live)) return;
+            unsigned wg = blockIdx.x;  // (opaque: see stat_verify)
+            asm volatile("" : "+s"(wg));
+            uint32_t *const slice = reinterpret_cast<uint32_t *>(a.c2v_scratch) + (size_t)wg * CK::kStatWords;
+            const uint32_t chg = ck.template stat_verify<decltype(words_c)::value>(slice, tid, (sc.vs(q_live) & 0xa) != 0);
+            // (split form: both halves of a state word are the one frame's, in half 0 of the control words)
+            constexpr bool kPacked = decltype(words_c)::value == CK::kStatSlots;
+            const uint32_t lo = kPacked ? chg & 0xffffu : chg, hi = kPacked ? chg >> 16 : 0u;
+            const uint32_t cb = (__ballot(lo != 0u) ? 0x10u : 0u) | (__ballot(hi != 0u) ? 0x20u : 0u);
+            if (cb) atomicOr(&misc[6 + s % 3], (int)cb);
+        }
+    };
     int cur = 0;
     int s = 1;
     bool more = true;
@@ -448,14 +534,14 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             misc[12] = 0;  // flag word of a final-update syndrome pass (below), read after this step's barrier
         }
         uint32_t par = 0, ovor = 0;
-        // When every frame in flight is at its last iteration (or the half is idle), this step only
-        // needs the syndrome of pc: the frames end here whatever it says, so the check update into pn
-        // (whose results nobody reads) is skipped -- max_iter updates per frame instead of max_iter + 1.
+        // (The check step always runs: a frame's last update is checked by the final-update syndrome pass
+        // below, not by one more step.)
 #if FPLDPC_WAIT_TRACE
         const unsigned long long wt0 = __builtin_amdgcn_s_memtime();
 #endif
         ck.step(a, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
         ovf |= ovor;
+        if constexpr (CK::kStationary) stat_check(std::integral_constant<int, CK::kStatSlots>{}, s);
         // per-step flags: fail (syndrome) for each half, OR over the block.  The int16 range flags
         // (ovf, sticky per lane until the half is refilled) are reduced only when a frame ends,
         // below: an overflow taints every frame in flight, and no frame is stored before that check
@@ -465,6 +551,8 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             uint32_t wb = 0;
 #pragma unroll
             for (int b = 0; b < 2; ++b) wb |= __ballot((bits >> b) & 1u) ? (1u << b) : 0u;
+            if constexpr (CK::kStationary)  // the trigger: par's other bits, the halves' posterior hashes changed
+                wb |= (__ballot((par & 0x7fffu) != 0u) ? 4u : 0u) | (__ballot((par & 0x7fff0000u) != 0u) ? 8u : 0u);
             if (wb) atomicOr(&misc[6 + s % 3], (int)wb);  // (wave-uniform: the atomic optimizer elects one lane)
         }
 #if FPLDPC_WAIT_TRACE
@@ -482,6 +570,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
         uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane(misc[6 + s % 3]);
         int finished = 0;
         if (!((flags & (uint32_t)q_live) == (uint32_t)q_live && s < q_until)) {
+            if constexpr (CK::kStationary) stat_decide(flags, s);
             // When no frame ends on pc's syndrome but every frame still running has just made its last
             // update (max_iter) into pn, check pn now (one syndrome pass after the barrier) instead of in
             // the next step's gather: a frame then costs max_iter check updates, not max_iter + 1.
@@ -495,6 +584,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                     const int d = s - sst(h);
                     const bool fail = flags >> h & 1u;
                     ends = ends || (d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter;
+                    if constexpr (CK::kStationary) ends = ends || (sc.stat >> h & 1);
                     any = true;
                     last = last && d + 1 == a.max_iter;
                 }
@@ -518,6 +608,10 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 const bool fail = flags >> h & 1u;
                 if ((d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter) ending |= 1 << h;
             }
+            if constexpr (CK::kStationary) {  // sexit: the halves that end by the stationary exit and by nothing else
+                sc.sexit = sc.stat & ~ending;
+                ending |= sc.sexit;
+            }
             if (ending) {
                 // the deferred int16 range check: a c2v at or above 2^b (a.cmax = 2^b - 1) in either half
                 // since that half's refill corrupts both halves' posterior words, so it taints every
@@ -533,7 +627,11 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 if (!(ending >> h & 1)) continue;
-                const int d = s - sst(h) + dadj;  // completed updates in pf for this frame
+                // completed updates in pf for this frame; a stationary frame reports the max_iter updates
+                // whose result pf (= pc, with pc's syndrome in flags: no final-update pass ran) holds
+                int d = s - sst(h) + dadj;
+                if constexpr (CK::kStationary)
+                    if (sc.sexit >> h & 1) d = a.max_iter;
                 const bool fail = flags >> h & 1u;
                 const bool pre = d == 0 && a.precheck && !fail;
                 finished |= 1 << h;
@@ -541,6 +639,8 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                     if (tid == 0) a.fb_list[atomicAdd(a.fb_count, 1)] = frm(h);
                 } else {
                     store(h, pre ? llrc : pf, pre, pre ? 0 : d, pre ? 1 : !fail);
+                    if constexpr (CK::kStationary)
+                        if ((sc.sexit >> h & 1) && tid == 0) misc[14] += 1;
                 }
             }
         }
@@ -558,7 +658,12 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 sst_r[h] = __builtin_amdgcn_readfirstlane(misc[2 + h]);
             }
             if constexpr (CK::kSplit) tail = a.split_tail && (frm(0) < 0) != (frm(1) < 0);
+            // (the exit's word rebuilt from the old one here, after the refill: the same value carried across
+            // the refill made the allocator copy the 47 state registers to a second set and back at every
+            // step -- 96 v_mov on the quick path, 3-4 % at points without stationary frames)
+            if constexpr (CK::kStationary) sc.vsk = (q_live & 0xc) | (sc.vs(q_live) & ~((finished & 1 ? 3 : 0) | (finished & 2 ? 12 : 0))) << 16;
             set_quick();
+            if constexpr (CK::kStationary) q_live = sc.word(q_live, (sc.vsk & 0xc) != 0, sc.vsk >> 16);
         }
 #if FPLDPC_WAIT_TRACE == 3
         wt_bar2 += __builtin_amdgcn_s_memtime() - wd0;
@@ -636,14 +741,16 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             misc[12] = 0;  // flag word of a final-update syndrome pass (below), read after this step's barrier
         }
         uint32_t par = 0, ovor = 0;
-        // When every frame in flight is at its last iteration (or the half is idle), this step only
-        // needs the syndrome of pc: the frames end here whatever it says, so the check update into pn
-        // (whose results nobody reads) is skipped -- max_iter updates per frame instead of max_iter + 1.
+        // (The check step always runs: a frame's last update is checked by the final-update syndrome pass
+        // below, not by one more step.)
         if constexpr (SPLIT)
             split_step_of(ck, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
         else
             ck.step(a, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
         ovf |= ovor;
+        if constexpr (CK::kStationary) {  // (nested: the outer condition does not depend on the lambda's parameter)
+            if constexpr (SPLIT) stat_check(std::integral_constant<int, CK::kStatSplitSlots>{}, s);
+        }
         // per-step flags: fail (syndrome) for each half, OR over the block.  The int16 range flags
         // (ovf, sticky per lane until the half is refilled) are reduced only when a frame ends,
         // below: an overflow taints every frame in flight, and no frame is stored before that check
@@ -653,6 +760,8 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             uint32_t wb = 0;
 #pragma unroll
             for (int b = 0; b < 2; ++b) wb |= __ballot((bits >> b) & 1u) ? (1u << b) : 0u;
+            if constexpr (CK::kStationary)  // (the trigger, as in the packed loop; the frame is in half 0)
+                wb |= __ballot((par & 0x7fffu) != 0u) ? 4u : 0u;
             if (lane == 0 && wb) atomicOr(&misc[6 + s % 3], (int)wb);
         }
         __syncthreads();
@@ -662,11 +771,17 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
                 if (frm(h) >= 0) q = q && (flags >> h & 1u) && s < sst(h) + a.max_iter - 1;
+            // (the stationary exit: the frame's posteriors changed, and no verification is pending)
+            if constexpr (CK::kStationary)
+                if (sc.on(q_live)) q = q && (flags >> 2 & 1u) && !sc.vs(q_live);
             if (q) {
                 cur = (cur + 1) % 3;
                 return true;
             }
         }
+        // (the stationary exit as in the packed loop; the frame is in half 0, and of the posterior words
+        // only that half is the frame's: half 1's `changed` and compare bits are never looked at)
+        if constexpr (CK::kStationary) stat_decide(flags, s);
         // When no frame ends on pc's syndrome but every frame still running has just made its last
         // update (max_iter) into pn, check pn now (one syndrome pass after the barrier) instead of in
         // the next step's gather: a frame then costs max_iter check updates, not max_iter + 1.
@@ -680,6 +795,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 const int d = s - sst(h);
                 const bool fail = flags >> h & 1u;
                 ends = ends || (d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter;
+                if constexpr (CK::kStationary) ends = ends || (sc.stat >> h & 1);
                 any = true;
                 last = last && d + 1 == a.max_iter;
             }
@@ -703,6 +819,10 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             const bool fail = flags >> h & 1u;
             if ((d == 0 && a.precheck && !fail) || (d >= 1 && a.early_term && !fail) || d >= a.max_iter) ending |= 1 << h;
         }
+        if constexpr (CK::kStationary) {
+            sc.sexit = sc.stat & ~ending;
+            ending |= sc.sexit;
+        }
         if (ending) {
             // the deferred int16 range check: a c2v at or above 2^b (a.cmax = 2^b - 1) in either half
             // since that half's refill corrupts both halves' posterior words, so it taints every
@@ -719,7 +839,9 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (!(ending >> h & 1)) continue;
-            const int d = s - sst(h) + dadj;  // completed updates in pf for this frame
+            int d = s - sst(h) + dadj;  // completed updates in pf for this frame (stationary: as in the packed loop)
+            if constexpr (CK::kStationary)
+                if (sc.sexit >> h & 1) d = a.max_iter;
             const bool fail = flags >> h & 1u;
             const bool pre = d == 0 && a.precheck && !fail;
             finished |= 1 << h;
@@ -727,10 +849,13 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 if (tid == 0) a.fb_list[atomicAdd(a.fb_count, 1)] = frm(h);
             } else {
                 store(h, pre ? llrc : pf, pre, pre ? 0 : d, pre ? 1 : !fail);
+                if constexpr (CK::kStationary)
+                    if ((sc.sexit >> h & 1) && tid == 0) misc[14] += 1;
             }
         }
         cur = (cur + 1) % 3;
         if (finished) {
+            if constexpr (CK::kStationary) q_live &= ~((finished & 1 ? 3 << 16 : 0) | (finished & 2 ? 12 << 16 : 0));
             refill(finished, s + 1, cur);
             // the refilled half starts from zero c2v state and a fresh range tracker.  (In the split
             // form the queue is empty -- a half goes idle only when a pull finds it so -- and this
@@ -777,12 +902,24 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 ovf &= 0xffffu;
             }
             ck.split_enter(h);
+            // (the scratch words are the packed state's: a pending verification starts over from the
+            // trigger, which a stationary frame sets again at every step)
+            if constexpr (CK::kStationary) q_live &= 0xffff;
 #if FPLDPC_TAIL_TRACE
             if (tid == 0) tt_split = __builtin_amdgcn_s_memrealtime();
 #endif
             __syncthreads();
             for (;; ++s)
                 if (!step_body(s, std::true_type{})) break;
+        }
+    }
+    if constexpr (CK::kStationary) {
+        // the call's stationary exits, in the counter block's list-1 size: a chain of two kernels has no
+        // second fallback list, and the chain's last kernel keeps that word for the host and zeroes it
+        // (chain_reset).  A returning atomic whose value is used, as chain_exit asks of counter accesses.
+        if (a.c2v_scratch && tid == 0 && misc[14]) {
+            const int was = atomicAdd(&a.counters[kCountFb1], misc[14]);
+            asm volatile("" ::"v"(was));
         }
     }
     if (a.totals && tid == 0) {  // this workgroup's frames (each counter < 2^31 per workgroup)

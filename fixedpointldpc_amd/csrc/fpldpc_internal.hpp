@@ -62,6 +62,7 @@ struct LaunchArgs {
     unsigned long long *probe = nullptr;  // diagnostic clock probe (host-mapped), or null
     unsigned long long *wgtrace = nullptr;  // diagnostic per-workgroup trace [grid][4] (host-mapped), or null
     int split_tail = 1;            // packed array kernels: a lone frame continues in the split form
+    int stationary_exit = 1;       // the A kernel ends frames whose messages have stopped changing (flood_pk)
 };
 
 enum class Variant { kNone, kArray47x2, kArray47x2og, kArray47x2c2, kArray47x2c2t, kArray47x2mix, kArray47, kLds16_47, kTab8x4lo3, kTab8x4p, kReg47x1Regular, kReg8x4, kReg8x1, kReg16x2, kGmem8, kGmem16, kGmem32, kGmem48, kGmem64 };
@@ -71,7 +72,7 @@ struct KernelChoice {
     int threads = 256;
     int grid = 0;            // resident workgroups (persistent)
     size_t lds_bytes = 0;
-    size_t scratch_ints = 0; // c2v scratch per launch (global variant)
+    size_t scratch_ints = 0; // c2v scratch per launch (global variant; the A kernel's stationary-exit slices)
     const char *name = "";
     Variant fallback = Variant::kNone;  // packed kernels: int32 re-decode of out-of-range frames
     int fb_grid = 0, fb_threads = 0;
@@ -87,6 +88,8 @@ struct KernelChoice {
 // Per-decoder device counter block (int32): [0] work counter, [1] first fallback's work counter,
 // [2] frames in fallback list 0, [3] second fallback's work counter, [4] frames in list 1,
 // [5] workgroups out of the call's last kernel, [6] / [7] the last call's list 0 / 1 sizes.
+// A chain of two kernels has no list 1: there the A kernel counts its stationary exits in [4], and [7]
+// holds the last call's (fpldpc_testing_stationary_exits; fpldpc_decoder_fallback_counts reports 0).
 // Zeroed once at decoder creation; the last workgroup of each call's last kernel resets [0..5]
 // (chain_exit, fpldpc_flood_device.hpp), so a decode call issues kernels only.
 constexpr int kCounterInts = 8;
@@ -143,6 +146,7 @@ struct fpldpc_decoder {
     int *d_fb_list = nullptr;      // fallback frame list of the packed kernels
     bool diag_probe = false;        // FPLDPC_CLOCK_PROBE=1 at creation
     bool split_tail = true;         // FPLDPC_SPLIT_TAIL=0 at creation: no split form in the tail (A/B runs)
+    bool stationary_exit = true;    // FPLDPC_STATIONARY_EXIT=0 at creation: every frame runs its iterations (A/B runs)
     std::string diag_trace_path;    // FPLDPC_WG_TRACE at creation
     int fb_cap = 0;
     int32_t *d_info_idx = nullptr;

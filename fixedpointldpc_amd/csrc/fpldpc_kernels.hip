@@ -53,6 +53,7 @@ struct VariantInfo {
     int tab_words = 0;      // LDS table words per check after the control words (array LDS offsets)
     int lo_passes = 0;      // > 0: checks listed by ascending degree, the first lo_passes * nt of degree dmin
     int chain_guard = 0;    // > 0: range guard from two chain values, needs chain_guard * C <= (cmax + 1) / 8
+    int stat_words = 0;     // > 0: flood_pk's stationary exit, this many scratch words per workgroup
 };
 
 size_t variant_lds(const VariantInfo &x, const fpldpc_code &c) {
@@ -67,9 +68,9 @@ const VariantInfo kVariants[] = {
     // A: the chain range guard (G = 24 C) while it is a small share of cmax, else the same kernel with
     // the per-output guard (chain_guard_ok)
     {Variant::kArray47x2, reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_kernel())), 47, kNT, true, false,
-     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47, kNT, false, 2, 0, 0, (47 - 1) / 2 + 1},
+     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47, kNT, false, 2, 0, 0, (47 - 1) / 2 + 1, ArrayChecks<47>::kStatWords},
     {Variant::kArray47x2og, reinterpret_cast<KernelFn>(const_cast<void *>(array47_pair_outguard_kernel())), 47, kNT, true, false,
-     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47},
+     "flood_array2<P=47,W=3>", 47, true, Variant::kArray47, kNT, false, 2, 0, 0, 0, ArrayChecks<47>::kStatWords},
     // p = 47 array codes with more than 256 checks, in one 768-thread workgroup at 3 waves / SIMD; the
     // first entry that fits the code is taken.  int16 range misses go to the LDS-state kernel and from
     // there to the global one.
@@ -224,7 +225,7 @@ int choose_kernel(const fpldpc_code &code, int device, int mask, int C, KernelCh
     out->grid = per_cu * prop.multiProcessorCount;
     out->fallback = pick->fallback;
     const int m_pad = (code.m + 63) / 64 * 64;
-    out->scratch_ints = pick->gmem ? (size_t)out->grid * pick->dc * m_pad : 0;
+    out->scratch_ints = pick->gmem ? (size_t)out->grid * pick->dc * m_pad : (size_t)out->grid * pick->stat_words;
     // a fallback kernel: rare work, so one workgroup per CU is plenty and exits fast when empty
     auto setup_fallback = [&](Variant v, int *grid, int *threads, size_t *lds_out) -> int {
         const VariantInfo *fb = find_variant(v);
@@ -319,12 +320,17 @@ int launch_decode(const KernelChoice &kc, const DeviceCode &dcode, const LaunchA
     a.fb_list = la.fb_list;
     a.fb_count = c + 2;
     a.cmax = kc.cmax;
+    // The stationary exit is on when the kernel gets its scratch (a slice of stat_words per workgroup
+    // of kc.grid, which no launch exceeds).  Its exit count rides in the list-1 size word, so the chain
+    // must be one without a second list.
+    if (vi->stat_words && !(la.stationary_exit && kc.fallback2 == Variant::kNone)) a.c2v_scratch = nullptr;
     const int per_wg = vi->lds_state ? 1 : 2;  // frames in flight per workgroup
     const int grid = std::min(kc.grid, (la.batch + per_wg - 1) / per_wg);
     hipLaunchKernelGGL(vi->fn, dim3(grid), dim3(kc.threads), kc.lds_bytes, s, a);
     e = hipGetLastError();
     if (e != hipSuccess) return launch_failed(e, "kernel launch");
     KArgs b = a;
+    b.c2v_scratch = la.c2v_scratch;
     b.last_in_chain = kc.fallback2 == Variant::kNone;
     b.frame_list = la.fb_list;
     b.frame_count = c + 2;

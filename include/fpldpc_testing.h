@@ -28,6 +28,13 @@ void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t ab
  * the range guard from two chain values (G = slots * C <= (cmax + 1) / 8) rather than per output. */
 uint32_t fpldpc_testing_range_guard(int32_t dv_max, int32_t C, int32_t slots, int32_t *chain_guard);
 
+/* The number of frames that the last completed fpldpc_decode call of `decoder` (an fpldpc_decoder_t)
+ * ended by the packed array kernel's stationary exit: frames whose check-to-variable messages were
+ * the same after two consecutive updates, reported with max_iter iterations and the outputs max_iter
+ * updates give.  0 for a decoder whose kernel has no such exit, or with FPLDPC_STATIONARY_EXIT=0 in
+ * the environment at its creation.  Returns an fpldpc status. */
+int fpldpc_testing_stationary_exits(void *decoder, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif
