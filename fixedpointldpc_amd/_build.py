@@ -21,6 +21,8 @@ SOURCES = [
     "fpldpc_kernels_w1.hip",
     "fpldpc_gen.hip",
     "fpldpc_float.hip",
+    # the test-only fpldpc_testing_float_describe: reads the float decoder's state, outside the build id
+    "fpldpc_float_describe.cpp",
     # the layered decoder: not in DEVICE_TUS / HASHED_TUS -- the build id covers the kernels with committed counters
     "fpldpc_layered.cpp",
     "fpldpc_layered.hip",

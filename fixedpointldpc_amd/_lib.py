@@ -138,6 +138,7 @@ def lib():
         "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
         "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
         "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
+        "fpldpc_testing_float_describe": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("FPLDPC_LIB_PATH") and not hasattr(L, name):
@@ -168,6 +169,7 @@ EXPORTED = [
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
     "fpldpc_testing_stationary_exits",  # include/fpldpc_testing.h: the last call's stationary exits
+    "fpldpc_testing_float_describe",  # include/fpldpc_testing.h: the float decoder's kernel form
 ]
 
 
@@ -291,6 +293,13 @@ class Decoder:
         c = ctypes.c_int32(0)
         _check(lib().fpldpc_testing_stationary_exits(self._h, ctypes.byref(c)))
         return c.value
+
+    def float_describe(self):
+        """The kernel decode_float_* launches, e.g. "bp_float_reg<DC=47,regular,array> grid=1024 planes=1"
+        (include/fpldpc_testing.h); builds the float tables by a one-frame decode if no float decode has run."""
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().fpldpc_testing_float_describe(self._h, buf, 256))
+        return buf.value.decode()
 
     def set_reference(self, info_index, info_bits):
         idx = np.ascontiguousarray(info_index, np.int32)

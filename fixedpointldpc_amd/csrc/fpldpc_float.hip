@@ -31,34 +31,9 @@
 
 #include "fpldpc_internal.hpp"
 #include "fpldpc_float_math.hpp"
+#include "fpldpc_float_state.hpp"
 
 namespace fpldpc {
-
-namespace {
-struct FArgs;
-}
-
-struct FloatState {
-    int device = -1;
-    int grid = 0;             // resident workgroups
-    size_t lds = 0;
-    void (*fn)(FArgs) = nullptr;
-    int32_t *d_cvar = nullptr;   // [dc_max][m] var of slot k of check c (-1 pad)
-    uint8_t *d_cdeg = nullptr;   // [m]
-    int32_t *d_vedge = nullptr;  // [dv_max][n] edge index slot*m + c of the k-th check of v
-    uint8_t *d_vdeg = nullptr;   // [n]
-    double *d_msg = nullptr;     // [grid][planes][dc_max * m]: edge messages (+ forward chain, generic kernel)
-    int planes = 2;
-    int *d_counter = nullptr;
-    ~FloatState() {
-        (void)hipFree(d_cvar);
-        (void)hipFree(d_cdeg);
-        (void)hipFree(d_vedge);
-        (void)hipFree(d_vdeg);
-        (void)hipFree(d_msg);
-        (void)hipFree(d_counter);
-    }
-};
 
 void free_float_state(FloatState *s) { delete s; }
 
@@ -850,11 +825,11 @@ int float_setup(fpldpc_decoder *dec) {
     // envelopes; the generic kernel (v2c and forward-chain planes in the scratch) otherwise
     s->planes = 1;
     if (dc == 47 && min_dc == 47) {
-        s->fn = H.array_forward ? bp_float_reg<47, true, true> : bp_float_reg<47, true>;
+        s->fn = H.array_forward ? (const void *)bp_float_reg<47, true, true> : (const void *)bp_float_reg<47, true>;
     } else if (dc <= 8 && min_dc >= 2) {
-        s->fn = bp_float_reg<8, false>;
+        s->fn = (const void *)bp_float_reg<8, false>;
     } else {
-        s->fn = bp_float_kernel;
+        s->fn = (const void *)bp_float_kernel;
         s->planes = 2;
     }
     std::vector<int32_t> cvar((size_t)dc * m, -1), vedge((size_t)dv * n, 0);
@@ -957,7 +932,7 @@ int fpldpc_decode_float(fpldpc_decoder_t dec, const double *llr, int32_t batch, 
     a.info_bits = dec->d_info_bits;
     a.k_info = dec->k_info;
     const int grid = std::min(s->grid, batch);
-    hipLaunchKernelGGL(s->fn, dim3(grid), dim3(kFT), s->lds, hs, a);
+    hipLaunchKernelGGL(reinterpret_cast<void (*)(FArgs)>(const_cast<void *>(s->fn)), dim3(grid), dim3(kFT), s->lds, hs, a);
     F_TRY(hipGetLastError());
     return FPLDPC_OK;
 }

@@ -35,6 +35,17 @@ uint32_t fpldpc_testing_range_guard(int32_t dv_max, int32_t C, int32_t slots, in
  * the environment at its creation.  Returns an fpldpc status. */
 int fpldpc_testing_stationary_exits(void *decoder, int32_t *count);
 
+/* Which kernel fpldpc_decode_float launches for `decoder` (an fpldpc_decoder_t), its persistent grid and
+ * the planes of its edge scratch, written to buf (at most len bytes) as one of
+ *   bp_float_reg<DC=47,regular,array> grid=N planes=1    regular degree 47, variable indices computed
+ *   bp_float_reg<DC=47,regular,table> grid=N planes=1    regular degree 47, indices from the table
+ *   bp_float_reg<DC=8,predicated,table> grid=N planes=1  check degrees 2..8
+ *   bp_float_kernel grid=N planes=2                      every other code
+ * The form is the name the HIP runtime gives the function the decoder launches, not a second statement
+ * of the choice.  A decoder that has not decoded yet builds its float tables first, by decoding one
+ * all-zero frame (FPLDPC_FLOAT_WG_PER_CU is read then).  Returns an fpldpc status. */
+int fpldpc_testing_float_describe(void *decoder, char *buf, int32_t len);
+
 #ifdef __cplusplus
 }
 #endif
