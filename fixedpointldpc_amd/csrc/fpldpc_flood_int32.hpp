@@ -13,6 +13,23 @@
 namespace fpldpc {
 namespace {
 
+// OR over the workgroup of a per-thread flag through a zeroed control word in the dynamic LDS, one
+// barrier.  (__syncthreads_or keeps 256 bytes of static LDS, which come out of the same 160 KiB as the
+// posteriors: with it the longest code was n = 10,219, not the 10,235 choose_kernel's length test admits.)
+__device__ __forceinline__ int block_or(int flag, int *word) {
+    if (__ballot(flag) && (threadIdx.x & 63) == 0) atomicOr(word, 1);
+    __syncthreads();
+    return *word;
+}
+// The same for step `it` of a frame, over the rotating flag words misc[2..4] (as flood_lds16 and flood_pk
+// do): thread 0 zeroes the next step's word before this step's barrier -- its last readers, at step
+// it - 2, have passed the barrier of step it - 1 -- so a step costs one barrier.  All three words are
+// zeroed at the frame pull.
+__device__ __forceinline__ int step_or(int fail, int *misc, int it) {
+    if (threadIdx.x == 0) misc[2 + (it + 1) % 3] = 0;
+    return block_or(fail, &misc[2 + it % 3]);
+}
+
 // Register-resident variant: CPL checks per lane (check c = tid + q*kNT), c2v and the packed
 // var indices of each check held in VGPRs for the lifetime of the workgroup.
 template <int DC, int CPL, bool REGULAR>
@@ -50,6 +67,7 @@ __global__ void __launch_bounds__(kNT) flood_reg(KArgs a) {
         if (tid == 0) {
             misc[0] = pull_frame(a, a.work_counter);
             misc[1] = 0;
+            misc[2] = misc[3] = misc[4] = 0;  // (step_or's flag words)
         }
         __syncthreads();
         const int cw = misc[0];
@@ -77,7 +95,7 @@ __global__ void __launch_bounds__(kNT) flood_reg(KArgs a) {
 #pragma unroll
             for (int q = 0; q < CPL; ++q)
                 if (act[q]) fail |= check_update<DC, REGULAR>(c2v[q], vpk[q], deg[q], pc, pn, update, a.C, a.mask);
-            fail = __syncthreads_or(fail);
+            fail = step_or(fail, misc, it);
             const int done = it - 1;
             if (done == 0 && a.precheck && !fail) {
                 pf = llr_s;
@@ -158,6 +176,7 @@ __global__ void __launch_bounds__(kNT) flood_gmem(KArgs a) {
         if (tid == 0) {
             misc[0] = pull_frame(a, a.work_counter);
             misc[1] = 0;
+            misc[2] = misc[3] = misc[4] = 0;  // (step_or's flag words)
         }
         __syncthreads();
         const int cw = misc[0];
@@ -179,7 +198,7 @@ __global__ void __launch_bounds__(kNT) flood_gmem(KArgs a) {
             int fail = 0;
             for (int c = tid; c < a.m; c += kNT)
                 fail |= check_update_gmem<DC>(c, a.cdeg[c], a.m_pad, a.vidx, c2vs, it == 1, pc, pn, update, a.C, a.mask);
-            fail = __syncthreads_or(fail);
+            fail = step_or(fail, misc, it);
             const int done = it - 1;
             if (done == 0 && a.precheck && !fail) {
                 pf = llr_s;
@@ -245,7 +264,7 @@ __global__ void __launch_bounds__(kNT) flood_edges(KArgs a, EdgeArgs e) {
         llr_s[v] = x;
         bufs[n + v] = x;  // posteriors of update 1: LLR + sum c2v
     }
-    if (tid == 0) misc[1] = 0;
+    if (tid == 0) misc[1] = misc[2] = misc[3] = misc[4] = misc[5] = 0;  // bit errors; step_or's words; the pre-check's
     __syncthreads();
     if (a.precheck) {  // hardDecision(LLR) (:270-294): a passing channel syndrome returns 0
         int fail = 0;
@@ -254,7 +273,7 @@ __global__ void __launch_bounds__(kNT) flood_edges(KArgs a, EdgeArgs e) {
             for (int k = 0; k < e.cdeg[c]; ++k) par ^= llr_s[vidx[(size_t)k * m + c]] <= 0;
             fail |= par;
         }
-        if (!__syncthreads_or(fail)) {
+        if (!block_or(fail, &misc[5])) {
             frame_store(a, 0, llr_s, false, 0, 1, misc);
             return;
         }
@@ -303,7 +322,7 @@ __global__ void __launch_bounds__(kNT) flood_edges(KArgs a, EdgeArgs e) {
                 lds_add(pn + vi[k], o);  // post' = LLR + sum c2v' (:131-144)
             }
         }
-        fail = __syncthreads_or(fail);
+        fail = step_or(fail, misc, it);
         const int done = it - 1;
         if ((done >= 1 && a.early_term && !fail) || done >= a.max_iter) {
             pf = pc;
@@ -364,6 +383,7 @@ __global__ void __launch_bounds__(kNT, 4) flood_array(KArgs a) {
         if (tid == 0) {
             misc[0] = pull_frame(a, a.work_counter);
             misc[1] = 0;
+            misc[2] = misc[3] = misc[4] = 0;  // (step_or's flag words)
         }
         __syncthreads();
         const int cw = misc[0];
@@ -439,7 +459,7 @@ __global__ void __launch_bounds__(kNT, 4) flood_array(KArgs a) {
                     // restore the c2v state (unused after the final syndrome, kept for clarity)
                 }
             }
-            fail = __syncthreads_or(fail);
+            fail = step_or(fail, misc, it);
             const int done = it - 1;
             if (done == 0 && a.precheck && !fail) {
                 pf = llr_s;

@@ -60,7 +60,11 @@ size_t variant_lds(const VariantInfo &x, const fpldpc_code &c) {
     size_t b = (size_t)(4 * c.n + kMiscInts) * sizeof(int);
     if (x.lds_state) b += (size_t)c.m * x.dc * sizeof(int16_t);
     b += (size_t)c.m * x.tab_words * sizeof(uint32_t);
-    b += 2 * (size_t)((c.n + 31) / 32) * sizeof(uint32_t);  // flood_pk: the info masks staged in LDS
+    // flood_pk: the info masks staged in LDS.  The int32 kernels (no fallback: flood_array, flood_reg,
+    // flood_gmem) use nothing past the control words and have no static LDS, so they are not charged for
+    // the masks: their longest code is the one choose_kernel's length test admits, (4 n + 20) * 4 <= 160 KiB,
+    // n = 10,235; the int16 kernels' envelopes stay as they were.
+    if (x.fallback != Variant::kNone) b += 2 * (size_t)((c.n + 31) / 32) * sizeof(uint32_t);
     return b;
 }
 
@@ -157,6 +161,13 @@ int choose_kernel(const fpldpc_code &code, int device, int mask, int C, KernelCh
             if (y->lds_state && C > kLds16MaxC) return false;
         return x.fallback == Variant::kNone || x.lds_state || cmax > 0;
     };
+    // the variant and every kernel of its fallback chain fit the LDS (setup_fallback makes each of them
+    // resident: p = 47 with 1363..1504 checks fits the walked CPL=2 kernel but not its LDS-state fallback)
+    auto lds_ok = [&](const VariantInfo &x) {
+        for (const VariantInfo *y = &x; y; y = y->fallback == Variant::kNone ? nullptr : find_variant(y->fallback))
+            if (variant_lds(*y, code) > 160 * 1024) return false;
+        return true;
+    };
     for (int r = 0; r < code.m; r++)
         if (code.cdeg[r] < 2) return fail(FPLDPC_ERR_UNSUPPORTED, "check of degree < 2 (reference behaviour undefined)");
     if (code.dc_max > 64) return fail(FPLDPC_ERR_UNSUPPORTED, "check degree above 64");
@@ -184,7 +195,7 @@ int choose_kernel(const fpldpc_code &code, int device, int mask, int C, KernelCh
         if (x.low_mask && !low_mask) continue;
         if (x.fallback != Variant::kNone && mask > 0xffff) continue;  // packed halves: mask within 16 bits
         if (!int16_ok(x)) continue;
-        if (variant_lds(x, code) > 160 * 1024) continue;
+        if (!lds_ok(x)) continue;
         if (min_dc < x.dmin) continue;
         if (x.regular ? !(regular && actual_dc == x.dc) : actual_dc > x.dc) continue;
         if (code.m > x.max_m) continue;
@@ -209,6 +220,13 @@ int choose_kernel(const fpldpc_code &code, int device, int mask, int C, KernelCh
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, dev);
     if (e != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
+    // a kernel's static LDS would come out of the same 160 KiB (none of the kernels has any today: the
+    // int32 kernels' block-wide OR goes through their control words, fpldpc_flood_int32.hpp block_or)
+    hipFuncAttributes fattr;
+    e = hipFuncGetAttributes(&fattr, (const void *)pick->fn);
+    if (e != hipSuccess) return fail_hip(e, "hipFuncGetAttributes");
+    if (lds + fattr.sharedSizeBytes > 160 * 1024)
+        return fail(FPLDPC_ERR_UNSUPPORTED, "code length too large for LDS-resident posteriors and the kernel's static LDS");
     if (lds > 64 * 1024) {
         e = hipFuncSetAttribute((const void *)pick->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute");

@@ -72,11 +72,7 @@ def test_generic_code_parity(F, O, torch_dev, name):
     ocode = O.OracleCode.from_alist_text(code.write_alist())
     rate = max(code.rate, 0.3)
     for mask in (0xFF, 0x3F):
-        try:
-            dec = F.Decoder(code, max_iter=20, width_mask=mask)
-        except F.FpldpcError as e:  # a code outside every kernel's envelope must say so, not decode wrong
-            assert e.code == -4, e
-            pytest.skip(f"{name}: {e}")
+        dec = F.Decoder(code, max_iter=20, width_mask=mask)  # (every code here lies inside the envelope)
         for i, eb in enumerate((1.0, 3.0, 6.0)):
             snr = 2 * math.pow(10.0, eb / 10) * rate
             llr = O.gen_llr(SEED, 100 * i, 48, code.n, snr, math.sqrt(1 / snr), 4)
