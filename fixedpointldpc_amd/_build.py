@@ -31,6 +31,8 @@ SOURCES = [
     "fpldpc_minsum.hip",
     # the global form of the two min-sum decoders (codes whose state does not fit LDS): outside the build id too
     "fpldpc_minsum_global.hip",
+    # the per-frame source of a simulation (information bits, their count against the decode): outside the build id too
+    "fpldpc_sim_source.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

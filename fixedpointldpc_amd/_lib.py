@@ -35,7 +35,8 @@ class SimParams(ctypes.Structure):
                 ("forced_index", ctypes.c_void_p), ("n_forced", ctypes.c_int32), ("forced_llr", ctypes.c_int32),
                 ("max_frame_errors", ctypes.c_int64), ("max_frames", ctypes.c_int64), ("count_mode", ctypes.c_int32),
                 ("chunk", ctypes.c_int32), ("host_threads", ctypes.c_int32), ("on_frame", ctypes.c_void_p),
-                ("on_frame_ctx", ctypes.c_void_p), ("device_channel", ctypes.c_int32)]
+                ("on_frame_ctx", ctypes.c_void_p), ("device_channel", ctypes.c_int32), ("random_info", ctypes.c_int32),
+                ("info_seed", ctypes.c_int64)]
 
 
 class SimResult(ctypes.Structure):
@@ -135,6 +136,14 @@ def lib():
         "fpldpc_sim_params_default": (None, [ctypes.POINTER(SimParams)]),
         "fpldpc_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
         "fpldpc_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult), P]),
+        "fpldpc_layered_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+        "fpldpc_layered_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
+                                                        P]),
+        "fpldpc_minsum_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+        "fpldpc_minsum_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
+                                                       P]),
+        "fpldpc_info_bits_host": (ctypes.c_int, [I64, I64, I32, I32, P]),
+        "fpldpc_info_bits": (ctypes.c_int, [I64, I64, I32, I32, P, P]),
         "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
         "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
         "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
@@ -166,6 +175,8 @@ EXPORTED = [
     "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
     "fpldpc_minsum_create", "fpldpc_minsum_destroy", "fpldpc_minsum_describe", "fpldpc_minsum_set_reference",
     "fpldpc_minsum_decode", "fpldpc_minsum_decode_host",
+    "fpldpc_layered_ber_sim", "fpldpc_layered_ber_sim_multi", "fpldpc_minsum_ber_sim", "fpldpc_minsum_ber_sim_multi",
+    "fpldpc_info_bits_host", "fpldpc_info_bits",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
     "fpldpc_testing_stationary_exits",  # include/fpldpc_testing.h: the last call's stationary exits
@@ -519,6 +530,15 @@ class LayeredDecoder:
             out["totals"] = tot
         return out
 
+    def ber_sim(self, snr, sigma, **kw):
+        """Ordered BER/FER simulation around this decoder (fpldpc_layered_ber_sim / fpldpc_minsum_ber_sim), as
+        Decoder.ber_sim.  Keywords: see sim_params()."""
+        p, keep = sim_params(snr, sigma, **kw)
+        r = SimResult()
+        _check(self._fn("ber_sim")(self._h, ctypes.byref(p), ctypes.byref(r)))
+        del keep
+        return {k: getattr(r, k) for k, _ in SimResult._fields_}
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             getattr(_lib, f"{self._abi}_destroy")(self._h)
@@ -616,6 +636,19 @@ def rng_skip(seed, draws):
     return int(lib().fpldpc_rng_skip(seed, draws))
 
 
+def info_bits(info_seed, first_frame, frames, k):
+    """The information bits of frames [first_frame, first_frame + frames) of a random_info simulation
+    (fpldpc_info_bits_host): uint8 [frames][k]."""
+    out = np.empty((max(frames, 0), max(k, 0)), np.uint8)
+    _check(lib().fpldpc_info_bits_host(info_seed, first_frame, frames, k, _ptr(out)))
+    return out
+
+
+def info_bits_ptrs(info_seed, first_frame, frames, k, out_ptr, stream=0):
+    """The same stream on the device (fpldpc_info_bits, async on `stream`) into uint8 [frames][k] device memory."""
+    _check(lib().fpldpc_info_bits(info_seed, first_frame, frames, k, out_ptr, stream or None))
+
+
 def channel_llr(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0):
     """Reference-harness LLRs (PerfTest.cpp:108-120) for frames [first_frame, first_frame+frames)."""
     out = np.empty((frames, n), dtype)
@@ -666,9 +699,11 @@ FPLDPC_COLL_AUTO, FPLDPC_COLL_RCCL, FPLDPC_COLL_HOST = 0, 1, 2
 
 def sim_params(snr, sigma, info_index=None, info_bits=None, codeword=None, seed=123456789, first_frame=0, frac_bits=4,
                max_frame_errors=100, max_frames=0, count_mode=FPLDPC_COUNT_BITS, forced_index=None, forced_llr=0,
-               chunk=0, host_threads=0, device_channel=False, on_frame=None):
+               chunk=0, host_threads=0, device_channel=False, on_frame=None, random_info=False, info_seed=987654321):
     """fpldpc_sim_params for fpldpc_ber_sim / fpldpc_ber_sim_multi; returns (params, keep-alive list).
-    on_frame(frame, iterations, blkerror) is called in frame order for every counted frame."""
+    on_frame(frame, iterations, blkerror) is called in frame order for every counted frame.
+    random_info: fresh information bits per frame from the stream info_bits(info_seed, ...), encoded on the
+    device (needs device_channel; no codeword, info_index, info_bits or forced_index)."""
     p = SimParams()
     lib().fpldpc_sim_params_default(ctypes.byref(p))
     keep = []
@@ -688,6 +723,7 @@ def sim_params(snr, sigma, info_index=None, info_bits=None, codeword=None, seed=
     p.forced_llr = forced_llr
     p.max_frame_errors, p.max_frames, p.count_mode = max_frame_errors, max_frames, count_mode
     p.chunk, p.host_threads, p.device_channel = chunk, host_threads, int(bool(device_channel))
+    p.random_info, p.info_seed = int(bool(random_info)), info_seed
     if on_frame is not None:
         cb = OnFrame(lambda ctx, f, it, blk: on_frame(f, it, blk))
         keep.append(cb)
@@ -697,13 +733,18 @@ def sim_params(snr, sigma, info_index=None, info_bits=None, codeword=None, seed=
 
 def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
-    host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host)."""
+    host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
+    The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix)."""
+    kinds = {type(d) for d in decoders}
+    if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
+        raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
+    fn = getattr(lib(), {Decoder: "fpldpc", LayeredDecoder: "fpldpc_layered", MinSumDecoder: "fpldpc_minsum"}[
+        kinds.pop()] + "_ber_sim_multi")
     p, keep = sim_params(snr, sigma, **kw)
     hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
     r = SimResult()
     used = ctypes.c_int32(0)
-    _check(lib().fpldpc_ber_sim_multi(hs, len(decoders), ctypes.byref(p), collective, ctypes.byref(r),
-                                      ctypes.byref(used)))
+    _check(fn(hs, len(decoders), ctypes.byref(p), collective, ctypes.byref(r), ctypes.byref(used)))
     del keep
     out = {k: getattr(r, k) for k, _ in SimResult._fields_}
     out["collective"] = used.value

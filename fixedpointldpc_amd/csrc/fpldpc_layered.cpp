@@ -48,6 +48,30 @@ void free_layered(fpldpc_layered *d) {
     delete d;
 }
 
+// The device side of a decoder whose code, parameters, device and choice are set: its tables, counter block,
+// scratch and stream (creation and layered_create_twin; on the decoder's device).
+int upload(fpldpc_layered *d) {
+    const fpldpc_code &c = d->code;
+    std::vector<uint8_t> cdeg(c.m);
+    for (int r = 0; r < c.m; r++) cdeg[r] = (uint8_t)c.cdeg[r];
+    HIP_TRY(hipMalloc(&d->d_cdeg, cdeg.size()));
+    HIP_TRY(hipMemcpy(d->d_cdeg, cdeg.data(), cdeg.size(), hipMemcpyHostToDevice));
+    if (!d->lc.computed) {
+        // slot-major index table in the code's own check order: vidx[k][c] = clist[c][k]; a layer's
+        // lanes read consecutive entries
+        std::vector<uint16_t> vidx((size_t)c.dc_max * c.m, 0);
+        for (int r = 0; r < c.m; r++)
+            for (int k = 0; k < c.cdeg[r]; k++) vidx[(size_t)k * c.m + r] = (uint16_t)c.clist[(size_t)r * c.dc_max + k];
+        HIP_TRY(hipMalloc(&d->d_vidx, vidx.size() * sizeof(uint16_t)));
+        HIP_TRY(hipMemcpy(d->d_vidx, vidx.data(), vidx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMalloc(&d->d_counter, kLayeredCounterInts * sizeof(int32_t)));  // zero between calls
+    HIP_TRY(hipMemset(d->d_counter, 0, kLayeredCounterInts * sizeof(int32_t)));
+    if (d->lc.scratch_bytes) HIP_TRY(hipMalloc(&d->d_scratch, d->lc.scratch_bytes));
+    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    return FPLDPC_OK;
+}
+
 // Constant = int((5.0/8.0) * (1 << FRAC_WIDTH)) (ArrayLDPCMacro.h:175)
 int constant_c(int frac_bits) { return (int)((5.0 / 8.0) * (1 << frac_bits)); }
 
@@ -117,29 +141,36 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
          : kind == kMinsum ? layered_minsum_choose(d->code, L, dev, &d->lc)
                            : layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
-    const fpldpc_code &c = d->code;
-    std::vector<uint8_t> cdeg(c.m);
-    for (int r = 0; r < c.m; r++) cdeg[r] = (uint8_t)c.cdeg[r];
-    HIP_TRY(hipMalloc(&d->d_cdeg, cdeg.size()));
-    HIP_TRY(hipMemcpy(d->d_cdeg, cdeg.data(), cdeg.size(), hipMemcpyHostToDevice));
-    if (!d->lc.computed) {
-        // slot-major index table in the code's own check order: vidx[k][c] = clist[c][k]; a layer's
-        // lanes read consecutive entries
-        std::vector<uint16_t> vidx((size_t)c.dc_max * c.m, 0);
-        for (int r = 0; r < c.m; r++)
-            for (int k = 0; k < c.cdeg[r]; k++) vidx[(size_t)k * c.m + r] = (uint16_t)c.clist[(size_t)r * c.dc_max + k];
-        HIP_TRY(hipMalloc(&d->d_vidx, vidx.size() * sizeof(uint16_t)));
-        HIP_TRY(hipMemcpy(d->d_vidx, vidx.data(), vidx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&d->d_counter, kLayeredCounterInts * sizeof(int32_t)));  // zero between calls
-    HIP_TRY(hipMemset(d->d_counter, 0, kLayeredCounterInts * sizeof(int32_t)));
-    if (d->lc.scratch_bytes) HIP_TRY(hipMalloc(&d->d_scratch, d->lc.scratch_bytes));
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    st = upload(d.get());
+    if (st) return st;
     *out = d.release();
     return FPLDPC_OK;
 }
 
 }  // namespace
+
+namespace fpldpc {
+int layered_create_twin(fpldpc_layered_t src, fpldpc_layered_t *out) {
+    if (!src || !out) return fail(FPLDPC_ERR_ARG, "null decoder");
+    DeviceGuard g(src->device);
+    if (!g.ok) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
+    std::unique_ptr<fpldpc_layered, void (*)(fpldpc_layered *)> d(new fpldpc_layered(), free_layered);
+    d->code = src->code;
+    d->params = src->params;
+    d->device = src->device;
+    d->L = src->L;
+    d->layers = src->layers;
+    d->post_bits = src->post_bits;
+    d->msg_bits = src->msg_bits;
+    d->scale_16 = src->scale_16;
+    d->offset = src->offset;
+    d->lc = src->lc;  // as chosen at src's creation: the environment is not read again
+    const int st = upload(d.get());
+    if (st) return st;
+    *out = d.release();
+    return FPLDPC_OK;
+}
+}  // namespace fpldpc
 
 extern "C" {
 

@@ -85,6 +85,11 @@ int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int sc
 bool minsum_state_forced_global(const char *env);
 int minsum_global_choose(const fpldpc_code &code, int device, LayeredChoice *lc);
 int minsum_global_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// A second layered object of src's code, parameters, L, layers, widths, scale, offset, device and LayeredChoice
+// (copied, not chosen again: the environment switches read at creation may have changed since), with device
+// tables, counter block, scratch and stream of its own: fpldpc_layered_ber_sim's and fpldpc_minsum_ber_sim's
+// second chunk in flight.  No reference bits.  Destroyed by fpldpc_layered_destroy.
+int layered_create_twin(fpldpc_layered_t src, fpldpc_layered_t *out);
 // Raises a kernel's dynamic-LDS limit on the current device, never lowers it (fpldpc_layered.hip).
 hipError_t raise_dynamic_lds(const void *fn, size_t bytes);
 

@@ -1,5 +1,5 @@
 // fpldpc_sim.cpp -- ordered BER/FER simulation around one or several GPU decoders
-// (fpldpc_ber_sim, fpldpc_ber_sim_multi).
+// (fpldpc_ber_sim, fpldpc_ber_sim_multi, and the same pair for the layered and the flooding min-sum decoder).
 //
 // The reference harness decodes one frame at a time and stops at the frame whose decode brings the
 // frame-error count to 100 (PerfTest.cpp:97-135, 275-311, 385-426, 485-511, 574-600).  Here frames
@@ -21,6 +21,10 @@
 // alone).  The exchange runs on a third stream.  Counters are unchanged: chunks are still counted
 // in round order, and a chunk decoded past the stop frame is drained, not counted.
 // FPLDPC_SIM_OVERLAP=0 submits each chunk after the previous round's exchange, on one decoder.
+//
+// random_info: each chunk's frames carry fresh information bits (fpldpc_sim_source.hip), encoded and sent
+// through the device channel with a codeword per frame, and the decode's hard decisions are counted against
+// them, all on the slot's stream (include/fpldpc.h); rounds, exchange and stop rule do not know of it.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -38,7 +42,9 @@
 #include <vector>
 
 #include "fpldpc_internal.hpp"
+#include "fpldpc_layered.hpp"
 #include "fpldpc_sim_plan.hpp"
+#include "fpldpc_sim_source.hpp"
 #include "fpldpc_testing.h"
 
 using namespace fpldpc;
@@ -51,6 +57,37 @@ namespace {
         if (_e != hipSuccess) return fail_hip((int)_e, #expr); \
     } while (0)
 
+// The decoder behind a rank or a slot: the six things the simulation asks of one, for fpldpc_decoder_t and
+// for fpldpc_layered_t (fpldpc_minsum_t enters as the layered object it wraps).
+struct Dec {
+    fpldpc_decoder_t flood = nullptr;
+    fpldpc_layered_t lay = nullptr;
+    explicit operator bool() const { return flood || lay; }
+    bool operator==(const Dec &o) const { return flood == o.flood && lay == o.lay; }
+    hipStream_t stream() const { return flood ? flood->stream : lay->stream; }
+    int device() const { return flood ? flood->device : lay->device; }
+    fpldpc_code &code() const { return flood ? flood->code : lay->code; }
+    int decode(const int16_t *llr, int32_t frames, uint32_t *hard, int32_t *iters, int32_t *bit_errors,
+               hipStream_t st) const {
+        return flood ? fpldpc_decode(flood, llr, FPLDPC_LLR_I16, frames, hard, iters, nullptr, nullptr, bit_errors, nullptr, st)
+                     : fpldpc_layered_decode(lay, llr, FPLDPC_LLR_I16, frames, hard, iters, nullptr, nullptr, bit_errors,
+                                             nullptr, st);
+    }
+    int set_reference(const int32_t *info_index, const uint8_t *info_bits, int32_t k) const {
+        return flood ? fpldpc_set_reference(flood, info_index, info_bits, k)
+                     : fpldpc_layered_set_reference(lay, info_index, info_bits, k);
+    }
+    int create_twin(Dec *out) const {
+        return flood ? decoder_create_twin(flood, &out->flood) : layered_create_twin(lay, &out->lay);
+    }
+    void destroy() {
+        if (flood) (void)fpldpc_decoder_destroy(flood);
+        if (lay) (void)fpldpc_layered_destroy(lay);
+        flood = nullptr;
+        lay = nullptr;
+    }
+};
+
 struct Slot {
     int16_t *h_llr = nullptr;
     int32_t *h_out = nullptr;  // [chunk] bit errors, [chunk] iterations, [1] int16 overflow count
@@ -59,13 +96,19 @@ struct Slot {
     hipEvent_t done = nullptr;
     int64_t frames = 0;
     int64_t first = 0;
-    fpldpc_decoder_t dec = nullptr;  // decodes this slot's chunks, on its own stream
+    Dec dec;  // decodes this slot's chunks, on its own stream
+    // random_info: the chunk's information bits [chunk][k], codewords [chunk][n] and hard decisions
+    // [chunk][hard words], and this stream's encoder (an encoder is single-stream)
+    uint8_t *d_info = nullptr;
+    uint8_t *d_cw = nullptr;
+    uint32_t *d_hard = nullptr;
+    fpldpc_encoder_t enc = nullptr;
 };
 
 // One rank: a decoder, its stream, two chunk slots.
 struct Rank {
-    fpldpc_decoder_t dec = nullptr;
-    fpldpc_decoder_t twin = nullptr;  // second decoder (two chunks in flight), owned here
+    Dec dec;
+    Dec twin;  // second decoder (two chunks in flight), owned here
     hipStream_t xs = nullptr;         // the exchange's stream when two chunks are in flight
     bool overlap = false;
     const fpldpc_sim_params *sp = nullptr;
@@ -73,16 +116,23 @@ struct Rank {
     Slot s[2];
     int32_t *d_forced = nullptr;
     const uint8_t *d_cw = nullptr;
+    int32_t *d_info_idx = nullptr;  // random_info: the encoder's info positions [k]
+    int k = 0;
     int64_t decoded = 0;
     ~Rank() {
         // a rank that left early (an error) may still have a chunk in flight: let it finish before
         // its buffers and the twin decoder go
         for (auto &x : s)
-            if (x.dec) (void)hipStreamSynchronize(x.dec->stream);
-        if (twin) (void)fpldpc_decoder_destroy(twin);
+            if (x.dec) (void)hipStreamSynchronize(x.dec.stream());
+        twin.destroy();
         if (xs) (void)hipStreamDestroy(xs);
         (void)hipFree(d_forced);
+        (void)hipFree(d_info_idx);
         for (auto &x : s) {
+            (void)hipFree(x.d_info);
+            (void)hipFree(x.d_cw);
+            (void)hipFree(x.d_hard);
+            if (x.enc) fpldpc_encoder_free(x.enc);
             (void)hipHostFree(x.h_llr);
             (void)hipHostFree(x.h_out);
             (void)hipFree(x.d_llr);
@@ -90,12 +140,12 @@ struct Rank {
             if (x.done) (void)hipEventDestroy(x.done);
         }
     }
-    hipStream_t exchange_stream() const { return xs ? xs : dec->stream; }
+    hipStream_t exchange_stream() const { return xs ? xs : dec.stream(); }
     int setup() {  // on the decoder's device
         const size_t llr_bytes = (size_t)chunk * n * sizeof(int16_t);
         s[0].dec = s[1].dec = dec;
         if (overlap) {
-            int st = decoder_create_twin(dec, &twin);
+            int st = dec.create_twin(&twin);
             if (st) return st;
             s[1].dec = twin;
             SIM_TRY(hipStreamCreateWithFlags(&xs, hipStreamNonBlocking));
@@ -118,11 +168,32 @@ struct Rank {
             if (sp->n_forced > 0)
                 SIM_TRY(hipMemcpy(d_forced, sp->forced_index, sizeof(int32_t) * sp->n_forced, hipMemcpyHostToDevice));
         }
+        if (sp->random_info) return setup_source();
         if (sp->count_mode == FPLDPC_COUNT_BITS) {
-            int st = fpldpc_set_reference(dec, sp->info_index, sp->info_bits, sp->k);
-            if (!st && twin) st = fpldpc_set_reference(twin, sp->info_index, sp->info_bits, sp->k);
+            int st = dec.set_reference(sp->info_index, sp->info_bits, sp->k);
+            if (!st && twin) st = twin.set_reference(sp->info_index, sp->info_bits, sp->k);
             return st;
         }
+        return FPLDPC_OK;
+    }
+    // random_info: per slot an encoder derived from the decoder's own code, warmed so that its device tables
+    // and packed-info scratch exist before the first chunk, and the chunk's info / codeword / hard buffers
+    int setup_source() {
+        const size_t hw = ((size_t)n + 31) / 32;
+        for (auto &x : s) {
+            int st = fpldpc_encoder_from_code(&dec.code(), &x.enc);
+            if (st) return st;
+            k = x.enc->k;
+            if (k < 1) return fail(FPLDPC_ERR_ARG, "random_info: the code has no information bits");
+            SIM_TRY(hipMalloc((void **)&x.d_info, (size_t)chunk * k));
+            SIM_TRY(hipMalloc((void **)&x.d_cw, (size_t)chunk * n));
+            SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hw * sizeof(uint32_t)));
+            SIM_TRY(hipMemsetAsync(x.d_info, 0, (size_t)chunk * k, x.dec.stream()));
+            if ((st = fpldpc_encoder_encode(x.enc, x.d_info, chunk, x.d_cw, x.dec.stream()))) return st;
+            SIM_TRY(hipStreamSynchronize(x.dec.stream()));
+        }
+        SIM_TRY(hipMalloc((void **)&d_info_idx, sizeof(int32_t) * k));
+        SIM_TRY(hipMemcpy(d_info_idx, s[0].enc->info_index.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice));
         return FPLDPC_OK;
     }
     // Host channel: the chunk's LLRs on host threads (device channel: in submit).
@@ -139,13 +210,19 @@ struct Rank {
     }
     int submit(Slot &x) {
         if (x.frames <= 0) return FPLDPC_OK;
-        hipStream_t st = x.dec->stream;
+        hipStream_t st = x.dec.stream();
         int r;
+        const bool count_bits = sp->count_mode == FPLDPC_COUNT_BITS;
         if (sp->device_channel) {
             int32_t *ovf = x.d_out + 2 * (size_t)chunk;
             SIM_TRY(hipMemsetAsync(ovf, 0, sizeof(int32_t), st));
-            if ((r = launch_channel(sp->seed, x.first, (int)x.frames, n, sp->snr, sp->sigma, sp->frac_bits, d_cw, 0,
-                                    x.d_llr, FPLDPC_LLR_I16, ovf, st)))
+            if (sp->random_info) {  // this chunk's information bits and their codewords, a codeword per frame
+                if ((r = fpldpc_info_bits(sp->info_seed, x.first, (int32_t)x.frames, k, x.d_info, st))) return r;
+                if ((r = fpldpc_encoder_encode(x.enc, x.d_info, (int32_t)x.frames, x.d_cw, st))) return r;
+            }
+            if ((r = launch_channel(sp->seed, x.first, (int)x.frames, n, sp->snr, sp->sigma, sp->frac_bits,
+                                    sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf,
+                                    st)))
                 return r;
             if (sp->n_forced > 0 &&
                 (r = launch_force_llr(x.d_llr, (int)x.frames, n, d_forced, sp->n_forced, (int16_t)sp->forced_llr, st)))
@@ -154,10 +231,14 @@ struct Rank {
         } else {
             SIM_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * sizeof(int16_t), hipMemcpyHostToDevice, st));
         }
-        r = fpldpc_decode(x.dec, x.d_llr, FPLDPC_LLR_I16, (int32_t)x.frames, nullptr, x.d_out + chunk, nullptr, nullptr,
-                          sp->count_mode == FPLDPC_COUNT_BITS ? x.d_out : nullptr, nullptr, st);
+        // random_info: the decoder has no reference; its hard decisions are counted against the chunk's own bits
+        r = x.dec.decode(x.d_llr, (int32_t)x.frames, sp->random_info ? x.d_hard : nullptr, x.d_out + chunk,
+                         count_bits && !sp->random_info ? x.d_out : nullptr, st);
         if (r) return r;
-        if (sp->count_mode == FPLDPC_COUNT_BITS)
+        if (count_bits && sp->random_info &&
+            (r = launch_count_info(x.d_hard, (n + 31) / 32, d_info_idx, x.d_info, k, (int)x.frames, x.d_out, st)))
+            return r;
+        if (count_bits)
             SIM_TRY(hipMemcpyAsync(x.h_out, x.d_out, (size_t)x.frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         SIM_TRY(hipMemcpyAsync(x.h_out + chunk, x.d_out + chunk, (size_t)x.frames * sizeof(int32_t),
                                hipMemcpyDeviceToHost, st));
@@ -240,11 +321,11 @@ struct Exchange {
         aborted = true;
         bar.abort();
     }
-    int init(const std::vector<fpldpc_decoder_t> &decs, bool injected_failure) {
+    int init(const std::vector<Dec> &decs, bool injected_failure) {
         if (!rccl) return FPLDPC_OK;
         if (injected_failure) return fail(FPLDPC_ERR_HIP, "ncclCommInitAll: injected failure (fpldpc_testing_sim_inject)");
         std::vector<int> devs(ndev);
-        for (int i = 0; i < ndev; ++i) devs[i] = decs[i]->device;
+        for (int i = 0; i < ndev; ++i) devs[i] = decs[i].device();
         comms.assign(ndev, nullptr);
         ncclResult_t r = ncclCommInitAll(comms.data(), ndev, devs.data());
         if (r != ncclSuccess) {
@@ -381,7 +462,7 @@ int rank_loop(Shared &sh, int rank) {
             err = fail(FPLDPC_ERR_HIP, "injected failure (fpldpc_testing_sim_inject)");
             own = fpldpc_last_error();
             if (sh.fail_abrupt) {
-                for (const Slot &z : R.s) (void)hipStreamSynchronize(z.dec->stream);
+                for (const Slot &z : R.s) (void)hipStreamSynchronize(z.dec.stream());
                 return err;
             }
         }
@@ -448,7 +529,7 @@ int rank_loop(Shared &sh, int rank) {
     total.add(unpack(red));
     // drain: a generated-but-not-submitted slot holds nothing on the device; a submitted one (two
     // chunks in flight, decoded past the stop frame) is waited for, not counted
-    for (const Slot &z : R.s) SIM_TRY(hipStreamSynchronize(z.dec->stream));
+    for (const Slot &z : R.s) SIM_TRY(hipStreamSynchronize(z.dec.stream()));
     SIM_TRY(hipStreamSynchronize(st));
     if (rank == 0) {
         sh.result = total;
@@ -457,14 +538,26 @@ int rank_loop(Shared &sh, int rank) {
     return FPLDPC_OK;
 }
 
-int validate(fpldpc_decoder_t dec, const fpldpc_sim_params *sp) {
-    const int n = dec->code.n;
+int validate(const Dec &dec, const fpldpc_sim_params *sp) {
+    const int n = dec.code().n;
     if (sp->max_frame_errors <= 0 && sp->max_frames <= 0)
         return fail(FPLDPC_ERR_ARG, "ber_sim needs max_frame_errors or max_frames");
     if (sp->count_mode != FPLDPC_COUNT_BITS && sp->count_mode != FPLDPC_COUNT_ITERS)
         return fail(FPLDPC_ERR_ARG, "bad count_mode");
-    if (sp->count_mode == FPLDPC_COUNT_BITS && (sp->k <= 0 || !sp->info_index || !sp->info_bits))
+    if (sp->random_info) {
+        if (sp->random_info != 1) return fail(FPLDPC_ERR_ARG, "random_info must be 0 or 1");
+        if (!sp->device_channel)
+            return fail(FPLDPC_ERR_ARG, "random_info needs device_channel = 1 (the host channel takes one codeword only)");
+        if (sp->codeword || sp->info_index || sp->info_bits)
+            return fail(FPLDPC_ERR_ARG,
+                        "random_info: codeword, info_index and info_bits must be NULL (the simulation owns them)");
+        if (sp->n_forced > 0)
+            return fail(FPLDPC_ERR_ARG, "random_info: no forced positions (shortening fixes information bits)");
+        if (sp->info_seed < 1 || sp->info_seed > 2147483646)
+            return fail(FPLDPC_ERR_ARG, "random_info: info_seed must be in 1 .. 2^31 - 2");
+    } else if (sp->count_mode == FPLDPC_COUNT_BITS && (sp->k <= 0 || !sp->info_index || !sp->info_bits)) {
         return fail(FPLDPC_ERR_ARG, "FPLDPC_COUNT_BITS needs info_index / info_bits");
+    }
     if (sp->n_forced < 0 || (sp->n_forced > 0 && !sp->forced_index)) return fail(FPLDPC_ERR_ARG, "bad forced list");
     for (int i = 0; i < sp->n_forced; i++)
         if (sp->forced_index[i] < 0 || sp->forced_index[i] >= n) return fail(FPLDPC_ERR_ARG, "forced index out of range");
@@ -480,19 +573,18 @@ struct DeviceRestore {
     }
 };
 
-int run_sim(const fpldpc_decoder_t *decs, int ndev, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out,
-            int32_t *used) {
-    if (!decs || ndev < 1 || !sp || !out) return fail(FPLDPC_ERR_ARG, "null argument");
+int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used) {
+    const int ndev = (int)dv.size();
+    if (ndev < 1 || !sp || !out) return fail(FPLDPC_ERR_ARG, "null argument");
     if (collective < FPLDPC_COLL_AUTO || collective > FPLDPC_COLL_HOST) return fail(FPLDPC_ERR_ARG, "bad collective");
-    std::vector<fpldpc_decoder_t> dv(decs, decs + ndev);
     bool distinct = true;
     for (int i = 0; i < ndev; ++i) {
         if (!dv[i]) return fail(FPLDPC_ERR_ARG, "null decoder");
-        if (dv[i]->code.n != dv[0]->code.n || dv[i]->code.m != dv[0]->code.m)
+        if (dv[i].code().n != dv[0].code().n || dv[i].code().m != dv[0].code().m)
             return fail(FPLDPC_ERR_ARG, "decoders of different codes");
         for (int j = 0; j < i; ++j) {
             if (dv[j] == dv[i]) return fail(FPLDPC_ERR_ARG, "the same decoder twice (a decoder is single-stream)");
-            distinct = distinct && dv[j]->device != dv[i]->device;
+            distinct = distinct && dv[j].device() != dv[i].device();
         }
         int st = validate(dv[i], sp);
         if (st) return st;
@@ -523,9 +615,9 @@ int run_sim(const fpldpc_decoder_t *decs, int ndev, const fpldpc_sim_params *sp,
         ranks[i]->dec = dv[i];
         ranks[i]->sp = sp;
         ranks[i]->chunk = sh.chunk;
-        ranks[i]->n = dv[i]->code.n;
+        ranks[i]->n = dv[i].code().n;
         ranks[i]->overlap = overlap;
-        if (hipSetDevice(dv[i]->device) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
+        if (hipSetDevice(dv[i].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         int st = ranks[i]->setup();
         if (st) return st;
         sh.ranks.push_back(ranks[i].get());
@@ -546,14 +638,14 @@ int run_sim(const fpldpc_decoder_t *decs, int ndev, const fpldpc_sim_params *sp,
     sh.status.assign(ndev, FPLDPC_OK);
     sh.message.assign(ndev, std::string());
     if (ndev == 1) {  // in the calling thread (its device and error state)
-        if (hipSetDevice(dv[0]->device) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
+        if (hipSetDevice(dv[0].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         st = rank_loop(sh, 0);
         if (st) return st;
     } else {
         std::vector<std::thread> th;
         for (int i = 0; i < ndev; ++i)
             th.emplace_back([&, i] {
-                if (hipSetDevice(dv[i]->device) != hipSuccess) {
+                if (hipSetDevice(dv[i].device()) != hipSuccess) {
                     sh.status[i] = fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
                 } else {
                     sh.status[i] = rank_loop(sh, i);
@@ -582,6 +674,25 @@ int run_sim(const fpldpc_decoder_t *decs, int ndev, const fpldpc_sim_params *sp,
     return FPLDPC_OK;
 }
 
+// The entry points' handles as Dec (a null handle stays a null Dec; no list at all is an empty one)
+Dec from(fpldpc_decoder_t d) {
+    Dec x;
+    x.flood = d;
+    return x;
+}
+Dec from(fpldpc_layered_t d) {
+    Dec x;
+    x.lay = d;
+    return x;
+}
+Dec from(fpldpc_minsum_t d) { return from(d ? d->lay : nullptr); }
+template <typename T>
+std::vector<Dec> from(const T *decs, int32_t ndev) {
+    std::vector<Dec> v;
+    for (int i = 0; decs && i < ndev; ++i) v.push_back(from(decs[i]));
+    return v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -593,16 +704,37 @@ void fpldpc_sim_params_default(fpldpc_sim_params *p) {
     p->frac_bits = 4;     // ArrayLDPCMacro.h:36
     p->max_frame_errors = 100;  // PerfTest.cpp:97
     p->count_mode = FPLDPC_COUNT_BITS;
+    p->info_seed = 987654321;
 }
 
 int fpldpc_ber_sim(fpldpc_decoder_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out) {
     if (!dec) return fail(FPLDPC_ERR_ARG, "null argument");
-    return run_sim(&dec, 1, sp, FPLDPC_COLL_HOST, out, nullptr);
+    return run_sim({from(dec)}, sp, FPLDPC_COLL_HOST, out, nullptr);
 }
 
 int fpldpc_ber_sim_multi(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
                          fpldpc_sim_result *out, int32_t *collective_used) {
-    return run_sim(decs, ndev, sp, collective, out, collective_used);
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used);
+}
+
+int fpldpc_layered_ber_sim(fpldpc_layered_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "null argument");
+    return run_sim({from(dec)}, sp, FPLDPC_COLL_HOST, out, nullptr);
+}
+
+int fpldpc_layered_ber_sim_multi(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used);
+}
+
+int fpldpc_minsum_ber_sim(fpldpc_minsum_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "null argument");
+    return run_sim({from(dec)}, sp, FPLDPC_COLL_HOST, out, nullptr);
+}
+
+int fpldpc_minsum_ber_sim_multi(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                                fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used);
 }
 
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init) {

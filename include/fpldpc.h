@@ -427,6 +427,8 @@ typedef struct {
     void *on_frame_ctx;
     int32_t device_channel;       /* 1 = generate the LLRs on the device (fpldpc_channel_llr) in the
                                      decoding stream instead of on host threads (default 0) */
+    int32_t random_info;          /* 1 = fresh information bits per frame, encoded on the device (default 0) */
+    int64_t info_seed;            /* Lehmer state of the information-bit stream (default 987654321) */
 } fpldpc_sim_params;
 
 typedef struct {
@@ -437,6 +439,38 @@ typedef struct {
 
 void fpldpc_sim_params_default(fpldpc_sim_params *p);
 int fpldpc_ber_sim(fpldpc_decoder_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out);
+/* The same simulation around a layered decoder (all three kinds: unsaturated, saturated with int16 or int32
+ * state, min-sum) and around the flooding min-sum decoder, in either placement of the min-sum state: the
+ * same chunks, stop rule, FPLDPC_SIM_OVERLAP switch and counters.  The twin is a second object of the same
+ * code, parameters, layering, widths, scale, offset and kernel choice (copied from `dec`, not chosen again:
+ * the environment switches read at creation are not read here), with its own tables, counter block, scratch
+ * (grid * slice bytes in the global placement) and stream: about the decoder's own footprint.  The int32
+ * envelope of the unsaturated layered decoder stays the caller's business, as for fpldpc_layered_decode. */
+int fpldpc_layered_ber_sim(fpldpc_layered_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out);
+int fpldpc_minsum_ber_sim(fpldpc_minsum_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out);
+
+/* A codeword per frame (fpldpc_sim_params.random_info = 1, on every fpldpc_*ber_sim* entry point).  The
+ * decoders are not symmetric at zero (a zero posterior or message counts as bit 1), so the error rate of one
+ * fixed codeword, the all-zero one above all, is biased by that codeword; with random_info every frame
+ * carries fresh information bits.  Per chunk, on the slot's stream: fpldpc_info_bits, the device encoder
+ * (derived from the decoder's own code as fpldpc_encoder_from_code does, one per slot), the device channel
+ * with a codeword per frame, the decode with its hard output, and a count of each frame's hard decisions at
+ * the encoder's info positions against the bits that frame was sent with (FPLDPC_COUNT_ITERS: no count,
+ * blkerror is the iteration count as ever).  FPLDPC_ERR_ARG, with a message naming the rule, unless
+ * device_channel = 1 (the host channel takes one codeword only), codeword, info_index and info_bits are
+ * NULL (the simulation owns them; k is ignored), n_forced = 0 (shortening fixes information bits) and
+ * 1 <= info_seed <= 2^31 - 2.  random_info = 0 ignores info_seed and changes nothing.
+ *
+ * The information-bit stream is public so that anyone can reproduce what was sent.  It is the reference's
+ * Lehmer generator (a = 48271, m = 2^31 - 1, fpldpc_rng_skip) started at info_seed, independent of the noise
+ * stream: bit i < k of frame f is (fpldpc_rng_skip(info_seed, (uint64_t)f * k + i + 1) >> 30) & 1, the state
+ * after draw f*k + i read as "uniform >= 1/2".  out is uint8 [frames][k] for frames [first_frame,
+ * first_frame + frames): host memory for fpldpc_info_bits_host; device memory, written asynchronously on
+ * `stream` (hipStream_t, NULL = default), for fpldpc_info_bits.  FPLDPC_ERR_ARG unless
+ * 1 <= info_seed <= 2^31 - 2, k >= 1, frames >= 0, first_frame >= 0 and (first_frame + frames) * k < 2^48
+ * (the device channel's limit on a draw index). */
+int fpldpc_info_bits_host(int64_t info_seed, int64_t first_frame, int32_t frames, int32_t k, uint8_t *out);
+int fpldpc_info_bits(int64_t info_seed, int64_t first_frame, int32_t frames, int32_t k, uint8_t *out_dev, void *stream);
 
 /* The same simulation over `ndev` decoders (one per device; SURVEY §8e: codeword batches shard
  * across the GPUs of a node), one host thread per decoder.  Frames go out in rounds: in round r
@@ -458,6 +492,11 @@ int fpldpc_ber_sim(fpldpc_decoder_t dec, const fpldpc_sim_params *sp, fpldpc_sim
 #define FPLDPC_COLL_HOST 2
 int fpldpc_ber_sim_multi(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
                          int32_t collective, fpldpc_sim_result *out, int32_t *collective_used);
+/* The same over layered decoders and over flooding min-sum decoders (fpldpc_layered_ber_sim above). */
+int fpldpc_layered_ber_sim_multi(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, fpldpc_sim_result *out, int32_t *collective_used);
+int fpldpc_minsum_ber_sim_multi(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                int32_t collective, fpldpc_sim_result *out, int32_t *collective_used);
 
 #ifdef __cplusplus
 }
