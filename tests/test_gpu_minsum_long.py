@@ -12,7 +12,9 @@ syndrome flags and posteriors exactly.
   * The frame framework of the global form, forced on small codes.
 Not covered here: the degree table read from global memory, which needs 2 n + 16 + m > 160 KiB (the
 smallest code of this family is n = 59,588, m = 44,691, which takes the loader minutes to parse); every
-code below stages its degrees in LDS."""
+code below stages its degrees in LDS.  tests/test_gpu_degree_edges.py, which runs every check degree at the
+edges of the kernels' DC buckets in every other form, leaves that one form out for the same reason: it
+exists only for codes of that length."""
 import re
 
 import numpy as np
