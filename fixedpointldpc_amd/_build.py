@@ -33,6 +33,8 @@ SOURCES = [
     "fpldpc_minsum_global.hip",
     # the per-frame source of a simulation (information bits, their count against the decode): outside the build id too
     "fpldpc_sim_source.hip",
+    # the harvest of a simulation's failing frames (scan and ordered compaction): outside the build id too
+    "fpldpc_harvest.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

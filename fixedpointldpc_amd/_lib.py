@@ -144,7 +144,20 @@ def lib():
                                                        P]),
         "fpldpc_info_bits_host": (ctypes.c_int, [I64, I64, I32, I32, P]),
         "fpldpc_info_bits": (ctypes.c_int, [I64, I64, I32, I32, P, P]),
+        "fpldpc_harvest_create": (ctypes.c_int, [P, I32, ctypes.POINTER(P)]),
+        "fpldpc_harvest_free": (None, [P]),
+        "fpldpc_harvest_scan": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
+        "fpldpc_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, ctypes.POINTER(SimResult), P]),
+        "fpldpc_layered_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
+                                                          ctypes.POINTER(SimResult), P]),
+        "fpldpc_minsum_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
+                                                         ctypes.POINTER(SimResult), P]),
+        "fpldpc_harvest_dims": (ctypes.c_int, [P, P]),
+        "fpldpc_harvest_counts": (ctypes.c_int, [P, P]),
+        "fpldpc_harvest_records": (ctypes.c_int, [P, I64, I64, P, P, P, P, P, P, P]),
+        "fpldpc_harvest_classes": (ctypes.c_int, [P, P, P, P, I32, ctypes.POINTER(I32)]),
         "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
+        "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
         "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
         "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
         "fpldpc_testing_float_describe": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
@@ -177,10 +190,14 @@ EXPORTED = [
     "fpldpc_minsum_decode", "fpldpc_minsum_decode_host",
     "fpldpc_layered_ber_sim", "fpldpc_layered_ber_sim_multi", "fpldpc_minsum_ber_sim", "fpldpc_minsum_ber_sim_multi",
     "fpldpc_info_bits_host", "fpldpc_info_bits",
+    "fpldpc_harvest_create", "fpldpc_harvest_free", "fpldpc_harvest_scan", "fpldpc_ber_sim_harvest",
+    "fpldpc_layered_ber_sim_harvest", "fpldpc_minsum_ber_sim_harvest", "fpldpc_harvest_dims", "fpldpc_harvest_counts",
+    "fpldpc_harvest_records", "fpldpc_harvest_classes",
     "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
     "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
     "fpldpc_testing_stationary_exits",  # include/fpldpc_testing.h: the last call's stationary exits
     "fpldpc_testing_float_describe",  # include/fpldpc_testing.h: the float decoder's kernel form
+    "fpldpc_testing_harvest_compact",  # include/fpldpc_testing.h: the harvest's ordered compaction on its own
 ]
 
 
@@ -428,9 +445,12 @@ class Decoder:
             out["totals"] = tot
         return out
 
-    def ber_sim(self, snr, sigma, **kw):
+    def ber_sim(self, snr, sigma, harvest=None, **kw):
         """Ordered BER/FER simulation (fpldpc_ber_sim): the reference harness's frame loop, batched.
-        Keywords: see sim_params()."""
+        Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
+        patterns (fpldpc_ber_sim_harvest), the filled Harvest under the result's "harvest" key."""
+        if harvest is not None:
+            return _harvest_sim("fpldpc", [self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
         p, keep = sim_params(snr, sigma, **kw)
         r = SimResult()
         _check(lib().fpldpc_ber_sim(self._h, ctypes.byref(p), ctypes.byref(r)))
@@ -530,9 +550,11 @@ class LayeredDecoder:
             out["totals"] = tot
         return out
 
-    def ber_sim(self, snr, sigma, **kw):
+    def ber_sim(self, snr, sigma, harvest=None, **kw):
         """Ordered BER/FER simulation around this decoder (fpldpc_layered_ber_sim / fpldpc_minsum_ber_sim), as
-        Decoder.ber_sim.  Keywords: see sim_params()."""
+        Decoder.ber_sim.  Keywords: see sim_params(); harvest as in Decoder.ber_sim."""
+        if harvest is not None:
+            return _harvest_sim(self._abi, [self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
         p, keep = sim_params(snr, sigma, **kw)
         r = SimResult()
         _check(self._fn("ber_sim")(self._h, ctypes.byref(p), ctypes.byref(r)))
@@ -731,15 +753,133 @@ def sim_params(snr, sigma, info_index=None, info_bits=None, codeword=None, seed=
     return p, keep
 
 
-def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, **kw):
+class Harvest:
+    """fpldpc_harvest_t: the failing frames of a simulation and their error patterns (include/fpldpc.h).
+    ber_sim(harvest=...) fills it; scan_torch is the device primitive on its own.  Per record i the numpy
+    fields frame, iters, info_errors, weight, unsat, err [hard_words] and syn [syn_words]; counts and classes
+    cover every counted frame whatever max_records is."""
+
+    COUNTS = ("frames", "codeword_errors", "detected", "undetected", "recorded", "dropped")
+
+    def __init__(self, code, max_records):
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_harvest_create(code._h if code is not None else None, max_records, ctypes.byref(h)))
+        self._h = h
+        self.code = code
+        self.max_records = max_records
+        dims = np.zeros(4, np.int32)
+        _check(lib().fpldpc_harvest_dims(self._h, _ptr(dims)))
+        self.n, self.m, self.hard_words, self.syn_words = (int(x) for x in dims)
+        self._fields = None
+
+    @property
+    def counts(self):
+        c = np.zeros(6, np.int64)
+        _check(lib().fpldpc_harvest_counts(self._h, _ptr(c)))
+        return dict(zip(self.COUNTS, (int(x) for x in c)))
+
+    @property
+    def classes(self):
+        """{(weight, unsat): frames}, in the order reported: by weight, then by unsat."""
+        n = ctypes.c_int32(0)
+        _check(lib().fpldpc_harvest_classes(self._h, None, None, None, 0, ctypes.byref(n)))
+        w, u, c = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.int64)
+        _check(lib().fpldpc_harvest_classes(self._h, _ptr(w), _ptr(u), _ptr(c), n.value, ctypes.byref(n)))
+        return {(int(a), int(b)): int(k) for a, b, k in zip(w, u, c)}
+
+    def records(self, first=0, count=None):
+        """Records [first, first + count) as a dict of numpy arrays (count None: all from first)."""
+        if count is None:
+            count = self.counts["recorded"] - first
+        k = max(count, 0)
+        out = {"frame": np.zeros(k, np.int64), "iters": np.zeros(k, np.int32), "info_errors": np.zeros(k, np.int32),
+               "weight": np.zeros(k, np.int32), "unsat": np.zeros(k, np.int32),
+               "err": np.zeros((k, self.hard_words), np.uint32), "syn": np.zeros((k, self.syn_words), np.uint32)}
+        _check(lib().fpldpc_harvest_records(self._h, first, count, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def _refresh(self):
+        self._fields = None
+
+    def __getattr__(self, name):
+        if name in ("frame", "iters", "info_errors", "weight", "unsat", "err", "syn"):
+            if self.__dict__.get("_fields") is None:
+                self._fields = self.records()
+            return self._fields[name]
+        raise AttributeError(name)
+
+    def error_positions(self, i):
+        """The wrong bits of record i, ascending."""
+        return np.nonzero(unpack_hard(self.err[i:i + 1], self.n)[0])[0]
+
+    def unsat_checks(self, i):
+        """The unsatisfied checks of record i, ascending."""
+        return np.nonzero(unpack_hard(self.syn[i:i + 1], self.m)[0])[0]
+
+    def scan_ptrs(self, hard_ptr, cw_ptr, cw_per_frame, batch, weight_ptr, unsat_ptr, err_ptr=0, syn_ptr=0, stream=0):
+        """fpldpc_harvest_scan on device pointers (ints, 0 = NULL), asynchronous on `stream`."""
+        c = ctypes.c_void_p
+        _check(lib().fpldpc_harvest_scan(self._h, c(hard_ptr or None), c(cw_ptr or None), cw_per_frame, batch,
+                                         c(weight_ptr or None), c(unsat_ptr or None), c(err_ptr or None),
+                                         c(syn_ptr or None), c(stream or None)))
+
+    def scan_torch(self, hard, cw=None, patterns=True):
+        """(weight, unsat, err, syn) of a [B][hard_words] int32 CUDA tensor of hard decisions against cw: None
+        (all-zero), a uint8 [n] tensor (shared) or [B][n] (per frame); on torch's current stream.  patterns=False
+        leaves err and syn out."""
+        import torch
+        assert hard.is_cuda and hard.dim() == 2 and hard.shape[1] == self.hard_words and hard.is_contiguous()
+        assert hard.dtype == torch.int32
+        B, dev, per = hard.shape[0], hard.device, 0
+        if cw is not None:
+            assert cw.dtype == torch.uint8 and cw.is_cuda and cw.is_contiguous()
+            per = 1 if cw.dim() == 2 else 0
+            assert cw.shape[-1] == self.n and (not per or cw.shape[0] == B)
+        out = {"weight": torch.empty(B, dtype=torch.int32, device=dev), "unsat": torch.empty(B, dtype=torch.int32, device=dev)}
+        if patterns:
+            out["err"] = torch.empty((B, self.hard_words), dtype=torch.int32, device=dev)
+            out["syn"] = torch.empty((B, self.syn_words), dtype=torch.int32, device=dev)
+        self.scan_ptrs(hard.data_ptr(), cw.data_ptr() if cw is not None else 0, per, B, out["weight"].data_ptr(),
+                       out["unsat"].data_ptr(), out["err"].data_ptr() if patterns else 0,
+                       out["syn"].data_ptr() if patterns else 0, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.fpldpc_harvest_free(self._h)
+            self._h = None
+
+
+def _harvest_sim(abi, decoders, snr, sigma, collective, harvest, kw):
+    """<abi>_ber_sim_harvest over `decoders`; harvest is a Harvest or max_records for a new one."""
+    hv = harvest if isinstance(harvest, Harvest) else Harvest(decoders[0].code, int(harvest))
+    p, keep = sim_params(snr, sigma, **kw)
+    hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
+    r = SimResult()
+    used = ctypes.c_int32(0)
+    hv._refresh()
+    _check(getattr(lib(), abi + "_ber_sim_harvest")(hs, len(decoders), ctypes.byref(p), collective, hv._h, ctypes.byref(r),
+                                                    ctypes.byref(used)))
+    del keep
+    out = {k: getattr(r, k) for k, _ in SimResult._fields_}
+    out["harvest"] = hv
+    return out, used.value
+
+
+def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
     host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
-    The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix)."""
+    The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix).
+    harvest as in Decoder.ber_sim."""
     kinds = {type(d) for d in decoders}
     if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
         raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
-    fn = getattr(lib(), {Decoder: "fpldpc", LayeredDecoder: "fpldpc_layered", MinSumDecoder: "fpldpc_minsum"}[
-        kinds.pop()] + "_ber_sim_multi")
+    abi = {Decoder: "fpldpc", LayeredDecoder: "fpldpc_layered", MinSumDecoder: "fpldpc_minsum"}[kinds.pop()]
+    if harvest is not None:
+        out, used = _harvest_sim(abi, decoders, snr, sigma, collective, harvest, kw)
+        out["collective"] = used
+        return out
+    fn = getattr(lib(), abi + "_ber_sim_multi")
     p, keep = sim_params(snr, sigma, **kw)
     hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
     r = SimResult()

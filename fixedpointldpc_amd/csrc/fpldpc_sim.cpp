@@ -25,6 +25,12 @@
 // random_info: each chunk's frames carry fresh information bits (fpldpc_sim_source.hip), encoded and sent
 // through the device channel with a codeword per frame, and the decode's hard decisions are counted against
 // them, all on the slot's stream (include/fpldpc.h); rounds, exchange and stop rule do not know of it.
+//
+// Harvest (the *_ber_sim_harvest entry points; fpldpc_harvest.hip): each chunk's decode writes its hard
+// decisions, and on the slot's stream, before its `done` event, the scan kernel gives every frame's (weight,
+// unsat) and err / syn row, the ordered compaction gathers the codeword-error frames' rows behind the pairs, and
+// one copy takes both to pinned memory.  After the stop decision rank 0's thread appends the ranks' chunks to the harvest in frame
+// order up to the stop frame, where on_frame is called.  Without a harvest none of this exists.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -41,6 +47,7 @@
 #include <thread>
 #include <vector>
 
+#include "fpldpc_harvest.hpp"
 #include "fpldpc_internal.hpp"
 #include "fpldpc_layered.hpp"
 #include "fpldpc_sim_plan.hpp"
@@ -103,6 +110,11 @@ struct Slot {
     uint8_t *d_cw = nullptr;
     uint32_t *d_hard = nullptr;
     fpldpc_encoder_t enc = nullptr;
+    // harvest: one block on the device and its pinned twin, copied once per chunk -- weight [frames], unsat
+    // [frames], then the compaction's records [min(cap, frames)][row words]; every frame's err | syn row
+    // [chunk][row words] and the compaction's scratch [chunk] stay on the device
+    int32_t *d_hv = nullptr, *h_hv = nullptr, *d_pos = nullptr;
+    uint32_t *d_rows = nullptr;
 };
 
 // One rank: a decoder, its stream, two chunk slots.
@@ -119,6 +131,10 @@ struct Rank {
     int32_t *d_info_idx = nullptr;  // random_info: the encoder's info positions [k]
     int k = 0;
     int64_t decoded = 0;
+    fpldpc_harvest *hv = nullptr;  // harvest: the object to fill (rank 0's thread does), or null
+    uint16_t *d_table = nullptr;   // this device's copy of its check table
+    uint8_t *d_hv_cw = nullptr;    // the fixed codeword [n] on the device where the host channel keeps it on the host
+    int cap = 0, row_words = 0;    // records per chunk buffer, words per record row (err | syn)
     ~Rank() {
         // a rank that left early (an error) may still have a chunk in flight: let it finish before
         // its buffers and the twin decoder go
@@ -128,7 +144,13 @@ struct Rank {
         if (xs) (void)hipStreamDestroy(xs);
         (void)hipFree(d_forced);
         (void)hipFree(d_info_idx);
+        (void)hipFree(d_table);
+        (void)hipFree(d_hv_cw);
         for (auto &x : s) {
+            (void)hipFree(x.d_hv);
+            (void)hipFree(x.d_pos);
+            (void)hipFree(x.d_rows);
+            (void)hipHostFree(x.h_hv);
             (void)hipFree(x.d_info);
             (void)hipFree(x.d_cw);
             (void)hipFree(x.d_hard);
@@ -168,6 +190,10 @@ struct Rank {
             if (sp->n_forced > 0)
                 SIM_TRY(hipMemcpy(d_forced, sp->forced_index, sizeof(int32_t) * sp->n_forced, hipMemcpyHostToDevice));
         }
+        if (hv) {
+            int st = setup_harvest();
+            if (st) return st;
+        }
         if (sp->random_info) return setup_source();
         if (sp->count_mode == FPLDPC_COUNT_BITS) {
             int st = dec.set_reference(sp->info_index, sp->info_bits, sp->k);
@@ -187,13 +213,57 @@ struct Rank {
             if (k < 1) return fail(FPLDPC_ERR_ARG, "random_info: the code has no information bits");
             SIM_TRY(hipMalloc((void **)&x.d_info, (size_t)chunk * k));
             SIM_TRY(hipMalloc((void **)&x.d_cw, (size_t)chunk * n));
-            SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hw * sizeof(uint32_t)));
+            if (!x.d_hard) SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hw * sizeof(uint32_t)));
             SIM_TRY(hipMemsetAsync(x.d_info, 0, (size_t)chunk * k, x.dec.stream()));
             if ((st = fpldpc_encoder_encode(x.enc, x.d_info, chunk, x.d_cw, x.dec.stream()))) return st;
             SIM_TRY(hipStreamSynchronize(x.dec.stream()));
         }
         SIM_TRY(hipMalloc((void **)&d_info_idx, sizeof(int32_t) * k));
         SIM_TRY(hipMemcpy(d_info_idx, s[0].enc->info_index.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice));
+        return FPLDPC_OK;
+    }
+    // harvest: this device's check table, per slot the hard decisions (random_info or not) and the buffers of
+    // the scan and the compaction
+    int setup_harvest() {
+        int st = harvest_upload_table(*hv, &d_table);
+        if (st) return st;
+        cap = std::min(hv->max_records, chunk);
+        row_words = hv->hard_words + hv->syn_words;
+        if (sp->codeword && !sp->device_channel) {
+            SIM_TRY(hipMalloc((void **)&d_hv_cw, n));
+            SIM_TRY(hipMemcpy(d_hv_cw, sp->codeword, n, hipMemcpyHostToDevice));
+        }
+        for (auto &x : s) {
+            SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hv->hard_words * sizeof(uint32_t)));
+            const size_t block = ((size_t)chunk * 2 + (size_t)cap * row_words) * sizeof(int32_t);
+            SIM_TRY(hipMalloc((void **)&x.d_hv, block));
+            SIM_TRY(hipHostMalloc((void **)&x.h_hv, block, hipHostMallocDefault));
+            if (cap > 0) {
+                SIM_TRY(hipMalloc((void **)&x.d_rows, (size_t)chunk * row_words * sizeof(uint32_t)));
+                SIM_TRY(hipMalloc((void **)&x.d_pos, (size_t)chunk * sizeof(int32_t)));
+            }
+        }
+        return FPLDPC_OK;
+    }
+    // after the chunk's decode, on its stream: scan and compaction, then the one copy the host appends from (the
+    // kernels first, so that the stream changes from kernels to copies once per chunk)
+    int submit_harvest(Slot &x, hipStream_t st) {
+        const int frames = (int)x.frames;
+        int32_t *weight = x.d_hv, *unsat = x.d_hv + frames;
+        size_t words = (size_t)frames * 2;
+        const uint8_t *cw = sp->random_info ? x.d_cw : d_hv_cw ? d_hv_cw : d_cw;
+        // once the harvest holds max_records records no later chunk's rows are read: weights only from then on
+        uint32_t *rows = cap > 0 && !hv->full.load(std::memory_order_relaxed) ? x.d_rows : nullptr;
+        int r = launch_harvest_scan(*hv, d_table, x.d_hard, cw, sp->random_info ? 1 : 0, frames, weight, unsat, rows,
+                                    row_words, rows ? rows + hv->hard_words : nullptr, row_words, st);
+        if (r) return r;
+        if (rows) {
+            const int c = std::min(cap, frames);
+            if ((r = launch_harvest_compact(weight, rows, row_words, frames, c, x.d_pos, (uint32_t *)(x.d_hv + words), st)))
+                return r;
+            words += (size_t)c * row_words;
+        }
+        SIM_TRY(hipMemcpyAsync(x.h_hv, x.d_hv, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         return FPLDPC_OK;
     }
     // Host channel: the chunk's LLRs on host threads (device channel: in submit).
@@ -232,12 +302,13 @@ struct Rank {
             SIM_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * sizeof(int16_t), hipMemcpyHostToDevice, st));
         }
         // random_info: the decoder has no reference; its hard decisions are counted against the chunk's own bits
-        r = x.dec.decode(x.d_llr, (int32_t)x.frames, sp->random_info ? x.d_hard : nullptr, x.d_out + chunk,
+        r = x.dec.decode(x.d_llr, (int32_t)x.frames, sp->random_info || hv ? x.d_hard : nullptr, x.d_out + chunk,
                          count_bits && !sp->random_info ? x.d_out : nullptr, st);
         if (r) return r;
         if (count_bits && sp->random_info &&
             (r = launch_count_info(x.d_hard, (n + 31) / 32, d_info_idx, x.d_info, k, (int)x.frames, x.d_out, st)))
             return r;
+        if (hv && (r = submit_harvest(x, st))) return r;
         if (count_bits)
             SIM_TRY(hipMemcpyAsync(x.h_out, x.d_out, (size_t)x.frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         SIM_TRY(hipMemcpyAsync(x.h_out + chunk, x.d_out + chunk, (size_t)x.frames * sizeof(int32_t),
@@ -397,7 +468,8 @@ struct Shared {
     int ndev = 1, chunk = 0;
     int64_t frame_end = 0;
     Exchange *ex = nullptr;
-    std::vector<Rank *> ranks;  // on_frame: rank 0's thread reads every rank's slot in frame order
+    std::vector<Rank *> ranks;  // on_frame, harvest: rank 0's thread reads every rank's slot in frame order
+    fpldpc_harvest *hv = nullptr;
     // per rank outcome
     std::vector<int> status;
     std::vector<std::string> message;
@@ -485,15 +557,24 @@ int rank_loop(Shared &sh, int rank) {
         std::vector<plan::Sums> sums(ndev);
         for (int i = 0; i < ndev; ++i) sums[i] = unpack(&all[(size_t)i * kWords]);
         const int sr = plan::stop_rank(sums.data(), ndev, total.frame_errors, need);
-        if (sp->on_frame) {  // frame order across ranks: rank 0's thread calls back for everyone
+        if (sp->on_frame || sh.hv) {  // frame order across ranks: rank 0's thread calls back and harvests for everyone
             if (!sh.ex->bar.wait()) return fail(FPLDPC_ERR_HIP, "another rank of the simulation failed");
             if (rank == 0) {
                 plan::Sums run = total;
                 for (int i = 0; i <= (sr < 0 ? ndev - 1 : sr); ++i) {
                     const Rank &Ri = *sh.ranks[i];
                     const Slot &xi = Ri.s[cur];
+                    int64_t rec = 0;  // the chunk's codeword-error frames so far: the next record of its buffer
                     for (int64_t f = 0; f < xi.frames; ++f) {
-                        sp->on_frame(sp->on_frame_ctx, xi.first + f, Ri.its(xi)[f], Ri.blk(xi)[f]);
+                        if (sp->on_frame) sp->on_frame(sp->on_frame_ctx, xi.first + f, Ri.its(xi)[f], Ri.blk(xi)[f]);
+                        if (sh.hv) {
+                            const int32_t w = xi.h_hv[f];
+                            const bool keep = w > 0 && rec < Ri.cap;  // add_frame reads the row of a record only
+                            const uint32_t *recs = (const uint32_t *)(xi.h_hv + 2 * xi.frames);
+                            sh.hv->add_frame(xi.first + f, Ri.its(xi)[f], Ri.blk(xi)[f], w, xi.h_hv[xi.frames + f],
+                                             keep ? recs + (size_t)rec * Ri.row_words : nullptr);
+                            rec += w > 0;
+                        }
                         run.add_frame(Ri.blk(xi)[f], Ri.its(xi)[f]);
                         if (i == sr && need > 0 && run.frame_errors >= need) break;
                     }
@@ -573,9 +654,14 @@ struct DeviceRestore {
     }
 };
 
-int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used) {
+// hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error
+int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used,
+            fpldpc_harvest *hv = nullptr, bool harvesting = false) {
     const int ndev = (int)dv.size();
     if (ndev < 1 || !sp || !out) return fail(FPLDPC_ERR_ARG, "null argument");
+    if (harvesting && !hv) return fail(FPLDPC_ERR_ARG, "null harvest");
+    if (hv && sp->count_mode != FPLDPC_COUNT_BITS)
+        return fail(FPLDPC_ERR_ARG, "a harvest needs count_mode = FPLDPC_COUNT_BITS");
     if (collective < FPLDPC_COLL_AUTO || collective > FPLDPC_COLL_HOST) return fail(FPLDPC_ERR_ARG, "bad collective");
     bool distinct = true;
     for (int i = 0; i < ndev; ++i) {
@@ -588,7 +674,11 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         }
         int st = validate(dv[i], sp);
         if (st) return st;
+        const fpldpc_code &c = dv[i].code();
+        if (hv && (hv->n != c.n || hv->m != c.m || hv->dc != c.dc_max || hv->clist != c.clist))
+            return fail(FPLDPC_ERR_ARG, "the harvest was made from another code than the decoders'");
     }
+    if (hv) hv->clear();
     static_assert(FPLDPC_COLL_AUTO == plan::kCollAuto && FPLDPC_COLL_RCCL == plan::kCollRccl &&
                   FPLDPC_COLL_HOST == plan::kCollHost, "collective codes");
     // (test hook: comm_init == 2 makes AUTO attempt RCCL with a single decoder, so that its fallback
@@ -603,6 +693,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
 
     Shared sh;
     sh.sp = sp;
+    sh.hv = hv;
     sh.ndev = ndev;
     sh.chunk = sp->chunk > 0 ? sp->chunk : 16384;
     if (sp->max_frames > 0) sh.chunk = (int)std::min<int64_t>(sh.chunk, sp->max_frames);
@@ -617,6 +708,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         ranks[i]->chunk = sh.chunk;
         ranks[i]->n = dv[i].code().n;
         ranks[i]->overlap = overlap;
+        ranks[i]->hv = hv;
         if (hipSetDevice(dv[i].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         int st = ranks[i]->setup();
         if (st) return st;
@@ -735,6 +827,23 @@ int fpldpc_minsum_ber_sim(fpldpc_minsum_t dec, const fpldpc_sim_params *sp, fpld
 int fpldpc_minsum_ber_sim_multi(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
                                 fpldpc_sim_result *out, int32_t *collective_used) {
     return run_sim(from(decs, ndev), sp, collective, out, collective_used);
+}
+
+int fpldpc_ber_sim_harvest(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                           fpldpc_harvest_t h, fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, true);
+}
+
+int fpldpc_layered_ber_sim_harvest(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                   int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                   int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, true);
+}
+
+int fpldpc_minsum_ber_sim_harvest(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                  int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, true);
 }
 
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init) {

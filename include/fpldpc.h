@@ -498,6 +498,73 @@ int fpldpc_layered_ber_sim_multi(const fpldpc_layered_t *decs, int32_t ndev, con
 int fpldpc_minsum_ber_sim_multi(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
                                 int32_t collective, fpldpc_sim_result *out, int32_t *collective_used);
 
+/* ---------------------------------------------------------------- harvest of the failing frames */
+/* What a simulation's counters do not say (no reference counterpart): which frames failed, and to what.  For
+ * one decoded frame let h be the hard decision (n bits) and c the word the frame was sent with -- the frame's
+ * own codeword under random_info, else fpldpc_sim_params.codeword, else all-zero.  Then
+ *     e = h XOR c,                          weight = |e|   (wrong bits)
+ *     s[k] = parity of h over check k,      unsat  = |s|   (unsatisfied checks; taken on h itself, not on e)
+ * and the frame is a codeword error when weight > 0: detected when unsat > 0 as well (the decoder ended
+ * outside the code), undetected when unsat = 0 (it ended on another codeword).  (weight, unsat) is the
+ * frame's class, the (a, b) of an absorbing-set profile.
+ *
+ * A harvest of a simulation covers exactly its counted frames, first_frame up to and including the stop
+ * frame, in frame order; nothing of a chunk decoded past the stop frame enters it.  It holds
+ *   records  one per codeword-error frame, the first max_records of them in frame order (a deterministic
+ *            choice): frame (int64), iterations, info_errors (the simulation's blkerror of that frame),
+ *            weight, unsat, err uint32[hard_words] (bit v % 32 of word v / 32, bits at or above n zero) and
+ *            syn uint32[ceil(m / 32)] (the same packing over checks, bits at or above m zero);
+ *   counts   int64[6] = {frames, codeword_errors, detected, undetected, recorded, dropped}, over all counted
+ *            frames whatever max_records is; dropped = codeword_errors - recorded;
+ *   classes  the distinct (weight, unsat) over all counted codeword-error frames with their frame counts,
+ *            sorted by weight, then by unsat; independent of max_records too.
+ * A record's frame index is enough to replay it: fpldpc_info_bits (first_frame = frame, frames = 1), the
+ * encoder and fpldpc_channel_llr (first_frame = frame, frames = 1) regenerate that frame's LLRs for any decoder.
+ *
+ * Per chunk and on the slot's stream, after the decode (called with its hard output) and before the slot is
+ * waited for: the scan kernel below over every frame, an ordered compaction of the codeword-error frames'
+ * err / syn rows into a buffer of min(max_records, chunk) records, and asynchronous copies to the host of
+ * 8 bytes per frame (weight, unsat) plus that buffer.  No host synchronisation is added.  Counts and classes
+ * accumulate on the host, where the stop frame is known. */
+typedef struct fpldpc_harvest *fpldpc_harvest_t;
+/* Host only, no GPU: copies the code's check lists.  FPLDPC_ERR_ARG unless code != NULL and
+ * 0 <= max_records <= 1 << 20. */
+int fpldpc_harvest_create(fpldpc_code_t code, int32_t max_records, fpldpc_harvest_t *out);
+void fpldpc_harvest_free(fpldpc_harvest_t h);
+/* The device primitive, asynchronous on `stream`, device pointers.  For each of `batch` frames: weight[f],
+ * unsat[f] and, where non-NULL, err[f][hard_words] and syn[f][syn_words] as defined above.  hard is
+ * [batch][hard_words] as fpldpc_decode writes it; bits >= n of the last word are IGNORED, whatever they hold.
+ * cw NULL = all-zero, else uint8 [n] (cw_per_frame = 0) or [batch][n] (cw_per_frame = 1), bit in the LSB.
+ * Binds to the current device on first use (uploads the check lists), like an encoder.  Touches no record. */
+int fpldpc_harvest_scan(fpldpc_harvest_t h, const uint32_t *hard, const uint8_t *cw, int32_t cw_per_frame,
+                        int32_t batch, int32_t *weight, int32_t *unsat, uint32_t *err, uint32_t *syn, void *stream);
+/* The simulation with a harvest: the _multi signatures plus h; ndev = 1 with FPLDPC_COLL_HOST is the single
+ * form.  The fpldpc_sim_result, the on_frame sequence and collective_used are exactly those of the matching
+ * *_ber_sim_multi call.  h is cleared when the call starts and filled when it returns FPLDPC_OK; after an
+ * error it stays a valid, freeable object with unspecified content.  FPLDPC_ERR_ARG, with a message naming
+ * the harvest, if h is NULL, if count_mode != FPLDPC_COUNT_BITS, or if h was made from a code whose n, m or
+ * check lists differ from the decoders'; every other rule of fpldpc_sim_params is as before, and so is every
+ * mode: host or device channel, all-zero, fixed or per-frame codeword, forced positions,
+ * FPLDPC_SIM_OVERLAP=0, several ranks with either collective (each rank uploads the check lists to its own
+ * device; one thread appends the ranks' chunks in frame order). */
+int fpldpc_ber_sim_harvest(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                           int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out, int32_t *collective_used);
+int fpldpc_layered_ber_sim_harvest(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                   int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                   int32_t *collective_used);
+int fpldpc_minsum_ber_sim_harvest(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                  int32_t *collective_used);
+/* dims = n, m, hard_words, syn_words */
+int fpldpc_harvest_dims(fpldpc_harvest_t h, int32_t dims[4]);
+int fpldpc_harvest_counts(fpldpc_harvest_t h, int64_t counts[6]);
+/* Copies records [first, first + count); any pointer may be NULL.  FPLDPC_ERR_ARG outside [0, recorded]. */
+int fpldpc_harvest_records(fpldpc_harvest_t h, int64_t first, int64_t count, int64_t *frame, int32_t *iters,
+                           int32_t *info_errors, int32_t *weight, int32_t *unsat, uint32_t *err, uint32_t *syn);
+/* *n_classes receives the number of classes; at most `cap` are copied. */
+int fpldpc_harvest_classes(fpldpc_harvest_t h, int32_t *weight, int32_t *unsat, int64_t *count, int32_t cap,
+                           int32_t *n_classes);
+
 #ifdef __cplusplus
 }
 #endif

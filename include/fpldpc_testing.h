@@ -46,6 +46,14 @@ int fpldpc_testing_stationary_exits(void *decoder, int32_t *count);
  * all-zero frame (FPLDPC_FLOAT_WG_PER_CU is read then).  Returns an fpldpc status. */
 int fpldpc_testing_float_describe(void *decoder, char *buf, int32_t len);
 
+/* The ordered compaction a harvesting simulation runs per chunk (include/fpldpc.h), on its own so that it can
+ * be tested and timed: rows [batch][row_words] of the frames with weight[f] > 0 go, in frame order, to
+ * rec [cap][row_words]; codeword-error frames beyond the first `cap` are left out, and records past the last
+ * one are not written.  pos [batch] is scratch (it receives each frame's record index, or -1).  Device
+ * pointers, asynchronous on `stream`.  Returns an fpldpc status. */
+int fpldpc_testing_harvest_compact(const int32_t *weight, const uint32_t *rows, int32_t row_words, int32_t batch,
+                                   int32_t cap, int32_t *pos, uint32_t *rec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
