@@ -23,6 +23,9 @@ SOURCES = [
     "fpldpc_float.hip",
     # the test-only fpldpc_testing_float_describe: reads the float decoder's state, outside the build id
     "fpldpc_float_describe.cpp",
+    # the host plumbing the decoder objects share (guard, creation checks, reference bits, staged host decode): no
+    # kernel reads it and it launches none, so it stays outside the build id
+    "fpldpc_host.cpp",
     # the layered decoder: not in DEVICE_TUS / HASHED_TUS -- the build id covers the kernels with committed counters
     "fpldpc_layered.cpp",
     "fpldpc_layered.hip",
@@ -51,7 +54,10 @@ DEVICE_TUS = ["fpldpc_kernels.hip", "fpldpc_kernels_a1.hip", "fpldpc_kernels_w1.
 SOURCE_FLAGS = {"fpldpc_kernels_a1.hip": ["-Xarch_device", "-mllvm=-disable-post-ra", "-Xarch_device", "-mllvm=-misched=ilpmax"],
                 "fpldpc_kernels.hip": ["-Xarch_device", "-mllvm=-amdgpu-use-amdgpu-trackers"],
                 "fpldpc_kernels_w1.hip": ["-Xarch_device", "-mllvm=-disable-post-ra"]}
-HASHED_TUS = DEVICE_TUS + ["fpldpc_decoder.cpp"]  # + the tables and launch arguments the kernels read
+# + the tables and launch arguments the kernels read.  fpldpc_decoder.cpp and the host tail of fpldpc_float.hip still
+# hold the flooding decoder's own staging, reference upload and describe, so an edit to those moves the id as well;
+# the layered and min-sum decoders' plumbing is fpldpc_host.cpp's, outside it.
+HASHED_TUS = DEVICE_TUS + ["fpldpc_decoder.cpp"]
 _PROBED = {}
 
 

@@ -49,6 +49,97 @@ FPLDPC_COUNT_ITERS = 1
 # void (*on_frame)(void *ctx, int64_t frame, int32_t iterations, int64_t blkerror)
 OnFrame = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64)
 
+# Result and argument types of every symbol include/*.h declares (tests/test_abi.py checks the names against the
+# headers); lib() sets them on the loaded library.
+P, I32, I64, U64, SZ = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
+SIGNATURES = {
+    "fpldpc_last_error": (ctypes.c_char_p, []),
+    "fpldpc_version": (ctypes.c_char_p, []),
+    "fpldpc_kernel_build_id": (ctypes.c_char_p, []),
+    "fpldpc_code_load_alist": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(P)]),
+    "fpldpc_code_parse_alist": (ctypes.c_int, [ctypes.c_char_p, SZ, ctypes.POINTER(P)]),
+    "fpldpc_code_array": (ctypes.c_int, [I32, I32, I32, ctypes.POINTER(P)]),
+    "fpldpc_code_wifi_1944_r12": (ctypes.c_int, [ctypes.POINTER(P)]),
+    "fpldpc_code_dims": (ctypes.c_int, [P, P]),
+    "fpldpc_code_rate": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_double)]),
+    "fpldpc_code_lists": (ctypes.c_int, [P, P, P, P, P]),
+    "fpldpc_code_write_alist": (ctypes.c_int, [P, ctypes.c_char_p, SZ, ctypes.POINTER(SZ)]),
+    "fpldpc_code_syndrome_host": (ctypes.c_int, [P, P]),
+    "fpldpc_code_free": (None, [P]),
+    "fpldpc_params_default": (None, [ctypes.POINTER(Params)]),
+    "fpldpc_decoder_create": (ctypes.c_int, [P, ctypes.POINTER(Params), ctypes.POINTER(P)]),
+    "fpldpc_decoder_destroy": (ctypes.c_int, [P]),
+    "fpldpc_decoder_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
+    "fpldpc_decoder_hard_words": (ctypes.c_int, [P]),
+    "fpldpc_decoder_fallback_counts": (ctypes.c_int, [P, P]),
+    "fpldpc_set_reference": (ctypes.c_int, [P, P, P, I32]),
+    "fpldpc_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
+    "fpldpc_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
+    "fpldpc_edge_ram_words": (ctypes.c_int, [P, ctypes.POINTER(I64)]),
+    "fpldpc_decode_frame": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
+    "fpldpc_decode_frame_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P]),
+    "fpldpc_code_layering": (ctypes.c_int, [P, I32, P]),
+    "fpldpc_layered_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, ctypes.POINTER(P)]),
+    "fpldpc_layered_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, ctypes.POINTER(P)]),
+    "fpldpc_layered_create_minsum": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, I32,
+                                                    ctypes.POINTER(P)]),
+    "fpldpc_layered_destroy": (ctypes.c_int, [P]),
+    "fpldpc_layered_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
+    "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
+    "fpldpc_layered_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
+    "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
+    "fpldpc_minsum_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, ctypes.POINTER(P)]),
+    "fpldpc_minsum_destroy": (ctypes.c_int, [P]),
+    "fpldpc_minsum_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
+    "fpldpc_minsum_set_reference": (ctypes.c_int, [P, P, P, I32]),
+    "fpldpc_minsum_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
+    "fpldpc_minsum_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
+    "fpldpc_rng_skip": (I64, [I64, U64]),
+    "fpldpc_channel_llr_host": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, P,
+                                               I32, I32]),
+    "fpldpc_encoder_load_g": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(P)]),
+    "fpldpc_encoder_from_code": (ctypes.c_int, [P, ctypes.POINTER(P)]),
+    "fpldpc_encoder_dims": (ctypes.c_int, [P, P]),
+    "fpldpc_encoder_info_index": (ctypes.c_int, [P, P, P]),
+    "fpldpc_unpack_info_bytes": (ctypes.c_int, [ctypes.c_char_p, I32, I32, P]),
+    "fpldpc_encoder_encode_host": (ctypes.c_int, [P, P, I32, P, I32]),
+    "fpldpc_encoder_encode": (ctypes.c_int, [P, P, I32, P, P]),
+    "fpldpc_decode_float": (ctypes.c_int, [P, P, I32, P, P, P, P, P, P, P]),
+    "fpldpc_decode_float_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P, P]),
+    "fpldpc_channel_llr": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P,
+                                          I32, P, P]),
+    "fpldpc_encoder_free": (None, [P]),
+    "fpldpc_sim_params_default": (None, [ctypes.POINTER(SimParams)]),
+    "fpldpc_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+    "fpldpc_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult), P]),
+    "fpldpc_layered_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+    "fpldpc_layered_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
+                                                    P]),
+    "fpldpc_minsum_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+    "fpldpc_minsum_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
+                                                   P]),
+    "fpldpc_info_bits_host": (ctypes.c_int, [I64, I64, I32, I32, P]),
+    "fpldpc_info_bits": (ctypes.c_int, [I64, I64, I32, I32, P, P]),
+    "fpldpc_harvest_create": (ctypes.c_int, [P, I32, ctypes.POINTER(P)]),
+    "fpldpc_harvest_free": (None, [P]),
+    "fpldpc_harvest_scan": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
+    "fpldpc_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, ctypes.POINTER(SimResult), P]),
+    "fpldpc_layered_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
+                                                      ctypes.POINTER(SimResult), P]),
+    "fpldpc_minsum_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
+                                                     ctypes.POINTER(SimResult), P]),
+    "fpldpc_harvest_dims": (ctypes.c_int, [P, P]),
+    "fpldpc_harvest_counts": (ctypes.c_int, [P, P]),
+    "fpldpc_harvest_records": (ctypes.c_int, [P, I64, I64, P, P, P, P, P, P, P]),
+    "fpldpc_harvest_classes": (ctypes.c_int, [P, P, P, P, I32, ctypes.POINTER(I32)]),
+    "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
+    "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
+    "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
+    "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
+    "fpldpc_testing_float_describe": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
+}
+EXPORTED = list(SIGNATURES)
+
 _lib = None
 
 
@@ -75,94 +166,7 @@ def lib():
             if not os.path.exists(path):
                 raise FpldpcError(-5, f"libfpldpc.so missing and build failed: {e}") from e
     L = ctypes.CDLL(path)
-    P, I32, I64, U64, SZ = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
-    sig = {
-        "fpldpc_last_error": (ctypes.c_char_p, []),
-        "fpldpc_version": (ctypes.c_char_p, []),
-        "fpldpc_kernel_build_id": (ctypes.c_char_p, []),
-        "fpldpc_code_load_alist": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(P)]),
-        "fpldpc_code_parse_alist": (ctypes.c_int, [ctypes.c_char_p, SZ, ctypes.POINTER(P)]),
-        "fpldpc_code_array": (ctypes.c_int, [I32, I32, I32, ctypes.POINTER(P)]),
-        "fpldpc_code_wifi_1944_r12": (ctypes.c_int, [ctypes.POINTER(P)]),
-        "fpldpc_code_dims": (ctypes.c_int, [P, P]),
-        "fpldpc_code_rate": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_double)]),
-        "fpldpc_code_lists": (ctypes.c_int, [P, P, P, P, P]),
-        "fpldpc_code_write_alist": (ctypes.c_int, [P, ctypes.c_char_p, SZ, ctypes.POINTER(SZ)]),
-        "fpldpc_code_syndrome_host": (ctypes.c_int, [P, P]),
-        "fpldpc_code_free": (None, [P]),
-        "fpldpc_params_default": (None, [ctypes.POINTER(Params)]),
-        "fpldpc_decoder_create": (ctypes.c_int, [P, ctypes.POINTER(Params), ctypes.POINTER(P)]),
-        "fpldpc_decoder_destroy": (ctypes.c_int, [P]),
-        "fpldpc_decoder_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
-        "fpldpc_decoder_hard_words": (ctypes.c_int, [P]),
-        "fpldpc_decoder_fallback_counts": (ctypes.c_int, [P, P]),
-        "fpldpc_set_reference": (ctypes.c_int, [P, P, P, I32]),
-        "fpldpc_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
-        "fpldpc_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
-        "fpldpc_edge_ram_words": (ctypes.c_int, [P, ctypes.POINTER(I64)]),
-        "fpldpc_decode_frame": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
-        "fpldpc_decode_frame_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P]),
-        "fpldpc_code_layering": (ctypes.c_int, [P, I32, P]),
-        "fpldpc_layered_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, ctypes.POINTER(P)]),
-        "fpldpc_layered_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, ctypes.POINTER(P)]),
-        "fpldpc_layered_create_minsum": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, I32,
-                                                        ctypes.POINTER(P)]),
-        "fpldpc_layered_destroy": (ctypes.c_int, [P]),
-        "fpldpc_layered_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
-        "fpldpc_layered_set_reference": (ctypes.c_int, [P, P, P, I32]),
-        "fpldpc_layered_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
-        "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
-        "fpldpc_minsum_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, ctypes.POINTER(P)]),
-        "fpldpc_minsum_destroy": (ctypes.c_int, [P]),
-        "fpldpc_minsum_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
-        "fpldpc_minsum_set_reference": (ctypes.c_int, [P, P, P, I32]),
-        "fpldpc_minsum_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
-        "fpldpc_minsum_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
-        "fpldpc_rng_skip": (I64, [I64, U64]),
-        "fpldpc_channel_llr_host": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, P,
-                                                   I32, I32]),
-        "fpldpc_encoder_load_g": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(P)]),
-        "fpldpc_encoder_from_code": (ctypes.c_int, [P, ctypes.POINTER(P)]),
-        "fpldpc_encoder_dims": (ctypes.c_int, [P, P]),
-        "fpldpc_encoder_info_index": (ctypes.c_int, [P, P, P]),
-        "fpldpc_unpack_info_bytes": (ctypes.c_int, [ctypes.c_char_p, I32, I32, P]),
-        "fpldpc_encoder_encode_host": (ctypes.c_int, [P, P, I32, P, I32]),
-        "fpldpc_encoder_encode": (ctypes.c_int, [P, P, I32, P, P]),
-        "fpldpc_decode_float": (ctypes.c_int, [P, P, I32, P, P, P, P, P, P, P]),
-        "fpldpc_decode_float_host": (ctypes.c_int, [P, P, I32, P, P, P, P, P, P]),
-        "fpldpc_channel_llr": (ctypes.c_int, [I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P,
-                                              I32, P, P]),
-        "fpldpc_encoder_free": (None, [P]),
-        "fpldpc_sim_params_default": (None, [ctypes.POINTER(SimParams)]),
-        "fpldpc_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
-        "fpldpc_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult), P]),
-        "fpldpc_layered_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
-        "fpldpc_layered_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
-                                                        P]),
-        "fpldpc_minsum_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
-        "fpldpc_minsum_ber_sim_multi": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, ctypes.POINTER(SimResult),
-                                                       P]),
-        "fpldpc_info_bits_host": (ctypes.c_int, [I64, I64, I32, I32, P]),
-        "fpldpc_info_bits": (ctypes.c_int, [I64, I64, I32, I32, P, P]),
-        "fpldpc_harvest_create": (ctypes.c_int, [P, I32, ctypes.POINTER(P)]),
-        "fpldpc_harvest_free": (None, [P]),
-        "fpldpc_harvest_scan": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
-        "fpldpc_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, ctypes.POINTER(SimResult), P]),
-        "fpldpc_layered_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
-                                                          ctypes.POINTER(SimResult), P]),
-        "fpldpc_minsum_ber_sim_harvest": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P,
-                                                         ctypes.POINTER(SimResult), P]),
-        "fpldpc_harvest_dims": (ctypes.c_int, [P, P]),
-        "fpldpc_harvest_counts": (ctypes.c_int, [P, P]),
-        "fpldpc_harvest_records": (ctypes.c_int, [P, I64, I64, P, P, P, P, P, P, P]),
-        "fpldpc_harvest_classes": (ctypes.c_int, [P, P, P, P, I32, ctypes.POINTER(I32)]),
-        "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
-        "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
-        "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
-        "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
-        "fpldpc_testing_float_describe": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         if os.environ.get("FPLDPC_LIB_PATH") and not hasattr(L, name):
             continue  # an older experimental build without this entry point
         f = getattr(L, name)
@@ -170,35 +174,6 @@ def lib():
         f.argtypes = args
     _lib = L
     return L
-
-
-# Every symbol include/*.h declares (checked by tests/test_abi.py).
-EXPORTED = [
-    "fpldpc_last_error", "fpldpc_version", "fpldpc_kernel_build_id", "fpldpc_code_load_alist", "fpldpc_code_parse_alist", "fpldpc_code_array",
-    "fpldpc_code_wifi_1944_r12", "fpldpc_code_dims", "fpldpc_code_rate", "fpldpc_code_lists",
-    "fpldpc_code_write_alist", "fpldpc_code_syndrome_host", "fpldpc_code_free", "fpldpc_params_default",
-    "fpldpc_decoder_create", "fpldpc_decoder_destroy", "fpldpc_decoder_describe", "fpldpc_decoder_hard_words",
-    "fpldpc_decoder_fallback_counts", "fpldpc_set_reference", "fpldpc_decode", "fpldpc_decode_host",
-    "fpldpc_edge_ram_words", "fpldpc_decode_frame", "fpldpc_decode_frame_host", "fpldpc_rng_skip", "fpldpc_channel_llr_host",
-    "fpldpc_sim_params_default", "fpldpc_ber_sim", "fpldpc_ber_sim_multi", "fpldpc_encoder_load_g", "fpldpc_encoder_from_code",
-    "fpldpc_encoder_dims", "fpldpc_encoder_info_index", "fpldpc_unpack_info_bytes", "fpldpc_encoder_encode_host",
-    "fpldpc_encoder_free", "fpldpc_encoder_encode", "fpldpc_channel_llr",
-    "fpldpc_decode_float", "fpldpc_decode_float_host",
-    "fpldpc_code_layering", "fpldpc_layered_create", "fpldpc_layered_create_sat", "fpldpc_layered_create_minsum", "fpldpc_layered_destroy", "fpldpc_layered_describe",
-    "fpldpc_layered_set_reference", "fpldpc_layered_decode", "fpldpc_layered_decode_host",
-    "fpldpc_minsum_create", "fpldpc_minsum_destroy", "fpldpc_minsum_describe", "fpldpc_minsum_set_reference",
-    "fpldpc_minsum_decode", "fpldpc_minsum_decode_host",
-    "fpldpc_layered_ber_sim", "fpldpc_layered_ber_sim_multi", "fpldpc_minsum_ber_sim", "fpldpc_minsum_ber_sim_multi",
-    "fpldpc_info_bits_host", "fpldpc_info_bits",
-    "fpldpc_harvest_create", "fpldpc_harvest_free", "fpldpc_harvest_scan", "fpldpc_ber_sim_harvest",
-    "fpldpc_layered_ber_sim_harvest", "fpldpc_minsum_ber_sim_harvest", "fpldpc_harvest_dims", "fpldpc_harvest_counts",
-    "fpldpc_harvest_records", "fpldpc_harvest_classes",
-    "fpldpc_testing_sim_inject",  # include/fpldpc_testing.h: test-only fault injection
-    "fpldpc_testing_range_guard",  # include/fpldpc_testing.h: the kernel choice's int16 range parameters
-    "fpldpc_testing_stationary_exits",  # include/fpldpc_testing.h: the last call's stationary exits
-    "fpldpc_testing_float_describe",  # include/fpldpc_testing.h: the float decoder's kernel form
-    "fpldpc_testing_harvest_compact",  # include/fpldpc_testing.h: the harvest's ordered compaction on its own
-]
 
 
 def _check(st):
@@ -290,57 +265,50 @@ class Code:
             self._h = None
 
 
-class Decoder:
-    """fpldpc_decoder_t: a batched GPU decoder for one code and one parameter set."""
+def _entries(family, **irregular):
+    """A decoder class's entry points: <family>_<method>, except where the ABI names them otherwise."""
+    names = ("destroy", "describe", "set_reference", "decode", "decode_host", "ber_sim", "ber_sim_multi", "ber_sim_harvest")
+    return {**{k: f"{family}_{k}" for k in names}, **irregular}
 
-    def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1):
+
+class _DecoderBase:
+    """What Decoder, LayeredDecoder and MinSumDecoder share: a handle made by the subclass's __init__ and the
+    methods every decoder object of the ABI has, through the class's table of entry-point names."""
+
+    _ENTRY = {}
+
+    def _fn(self, name):
+        return getattr(lib(), self._ENTRY[name])
+
+    def _adopt(self, code, handle, params):
+        self.code, self.params, self._h = code, params, handle
+        self.hard_words = (code.n + 31) // 32
+
+    @staticmethod
+    def _params(max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1):
         p = Params()
         lib().fpldpc_params_default(ctypes.byref(p))
         p.max_iter, p.frac_bits, p.width_mask = max_iter, frac_bits, width_mask
         p.early_term, p.precheck, p.device = int(bool(early_term)), int(bool(precheck)), device
-        self.code = code
-        self.params = p
-        h = ctypes.c_void_p()
-        _check(lib().fpldpc_decoder_create(code._h, ctypes.byref(p), ctypes.byref(h)))
-        self._h = h
-        self.hard_words = lib().fpldpc_decoder_hard_words(self._h)
+        return p
 
     def describe(self):
         buf = ctypes.create_string_buffer(256)
-        _check(lib().fpldpc_decoder_describe(self._h, buf, 256))
-        return buf.value.decode()
-
-    def fallback_counts(self):
-        """(first, second) fallback-kernel frame counts of the last completed decode call."""
-        c = np.zeros(2, np.int32)
-        _check(lib().fpldpc_decoder_fallback_counts(self._h, _ptr(c)))
-        return int(c[0]), int(c[1])
-
-    def stationary_exits(self):
-        """Frames the last completed decode call ended by the stationary exit (include/fpldpc_testing.h)."""
-        c = ctypes.c_int32(0)
-        _check(lib().fpldpc_testing_stationary_exits(self._h, ctypes.byref(c)))
-        return c.value
-
-    def float_describe(self):
-        """The kernel decode_float_* launches, e.g. "bp_float_reg<DC=47,regular,array> grid=1024 planes=1"
-        (include/fpldpc_testing.h); builds the float tables by a one-frame decode if no float decode has run."""
-        buf = ctypes.create_string_buffer(256)
-        _check(lib().fpldpc_testing_float_describe(self._h, buf, 256))
+        _check(self._fn("describe")(self._h, buf, 256))
         return buf.value.decode()
 
     def set_reference(self, info_index, info_bits):
         idx = np.ascontiguousarray(info_index, np.int32)
         bits = np.ascontiguousarray(info_bits, np.uint8)
-        _check(lib().fpldpc_set_reference(self._h, _ptr(idx), _ptr(bits), len(idx)))
+        _check(self._fn("set_reference")(self._h, _ptr(idx), _ptr(bits), len(idx)))
 
     def decode_ptrs(self, llr_ptr, llr_type, batch, hard=0, iters=0, syn_ok=0, post=0, bit_errors=0, totals=0,
                     stream=0):
         """Asynchronous decode on device pointers (ints); stream is a hipStream_t as int."""
         c = ctypes.c_void_p
-        _check(lib().fpldpc_decode(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
-                                   c(syn_ok or None), c(post or None), c(bit_errors or None), c(totals or None),
-                                   c(stream or None)))
+        _check(self._fn("decode")(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
+                                  c(syn_ok or None), c(post or None), c(bit_errors or None), c(totals or None),
+                                  c(stream or None)))
 
     def decode_torch(self, llr, post=False, bit_errors=False, totals=None, stream=None):
         """Decode a [B][n] int16/int32 CUDA tensor; returns a dict of output tensors.
@@ -379,6 +347,82 @@ class Decoder:
                          out["bit_errors"].data_ptr() if bit_errors else 0,
                          totals.data_ptr() if totals is not None else 0, s.cuda_stream)
         return out
+
+    def decode_host(self, llr, post=None, bit_errors=False, totals=None):
+        """Synchronous decode of a host [B][n] int16/int32 array; returns numpy outputs."""
+        llr = np.ascontiguousarray(llr)
+        assert llr.ndim == 2 and llr.shape[1] == self.code.n and llr.dtype in (np.int16, np.int32)
+        B = llr.shape[0]
+        llr_type = FPLDPC_LLR_I16 if llr.dtype == np.int16 else FPLDPC_LLR_I32
+        hard = np.zeros((B, self.hard_words), np.uint32)
+        iters = np.zeros(B, np.int32)
+        ok = np.zeros(B, np.uint8)
+        post_arr = None
+        if post is not None:
+            post_arr = np.ascontiguousarray(post, np.int32) if not isinstance(post, bool) else np.zeros(
+                (B, self.code.n), np.int32)
+        be = np.zeros(B, np.int32) if bit_errors else None
+        tot = None if totals is None else np.ascontiguousarray(totals, np.int64)
+        _check(self._fn("decode_host")(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok), _ptr(post_arr),
+                                       _ptr(be), _ptr(tot)))
+        out = {"hard": hard, "iters": iters, "syndrome_ok": ok}
+        if post_arr is not None:
+            out["post"] = post_arr
+        if be is not None:
+            out["bit_errors"] = be
+        if tot is not None:
+            out["totals"] = tot
+        return out
+
+    def ber_sim(self, snr, sigma, harvest=None, **kw):
+        """Ordered BER/FER simulation around this decoder (fpldpc_ber_sim, fpldpc_layered_ber_sim,
+        fpldpc_minsum_ber_sim): the reference harness's frame loop, batched.
+        Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
+        patterns (<family>_ber_sim_harvest), the filled Harvest under the result's "harvest" key."""
+        if harvest is not None:
+            return _harvest_sim([self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
+        p, keep = sim_params(snr, sigma, **kw)
+        r = SimResult()
+        _check(self._fn("ber_sim")(self._h, ctypes.byref(p), ctypes.byref(r)))
+        del keep
+        return {k: getattr(r, k) for k, _ in SimResult._fields_}
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            getattr(_lib, self._ENTRY["destroy"])(self._h)
+            self._h = None
+
+
+class Decoder(_DecoderBase):
+    """fpldpc_decoder_t: a batched GPU decoder for one code and one parameter set."""
+
+    _ENTRY = _entries("fpldpc", destroy="fpldpc_decoder_destroy", describe="fpldpc_decoder_describe")
+
+    def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1):
+        p = self._params(max_iter, frac_bits, width_mask, early_term, precheck, device)
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_decoder_create(code._h, ctypes.byref(p), ctypes.byref(h)))
+        self._adopt(code, h, p)
+        self.hard_words = lib().fpldpc_decoder_hard_words(self._h)
+
+    def fallback_counts(self):
+        """(first, second) fallback-kernel frame counts of the last completed decode call."""
+        c = np.zeros(2, np.int32)
+        _check(lib().fpldpc_decoder_fallback_counts(self._h, _ptr(c)))
+        return int(c[0]), int(c[1])
+
+    def stationary_exits(self):
+        """Frames the last completed decode call ended by the stationary exit (include/fpldpc_testing.h)."""
+        c = ctypes.c_int32(0)
+        _check(lib().fpldpc_testing_stationary_exits(self._h, ctypes.byref(c)))
+        return c.value
+
+    def float_describe(self):
+        """The kernel decode_float_* launches, e.g. "bp_float_reg<DC=47,regular,array> grid=1024 planes=1"
+        (include/fpldpc_testing.h); builds the float tables by a one-frame decode if no float decode has run."""
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().fpldpc_testing_float_describe(self._h, buf, 256))
+        return buf.value.decode()
 
     def decode_float_torch(self, llr, post=False, bit_errors=False, totals=None, stream=None):
         """Floating-point BP decode (fpldpc_decode_float) of a [B][n] float64 CUDA tensor."""
@@ -419,51 +463,8 @@ class Decoder:
                                               _ptr(be), _ptr(tot)))
         return {"hard": hard, "iters": iters, "syndrome_ok": ok, "post": p, "bit_errors": be, "totals": tot}
 
-    def decode_host(self, llr, post=None, bit_errors=False, totals=None):
-        """Synchronous decode of a host [B][n] int16/int32 array; returns numpy outputs."""
-        llr = np.ascontiguousarray(llr)
-        assert llr.ndim == 2 and llr.shape[1] == self.code.n and llr.dtype in (np.int16, np.int32)
-        B = llr.shape[0]
-        llr_type = FPLDPC_LLR_I16 if llr.dtype == np.int16 else FPLDPC_LLR_I32
-        hard = np.zeros((B, self.hard_words), np.uint32)
-        iters = np.zeros(B, np.int32)
-        ok = np.zeros(B, np.uint8)
-        post_arr = None
-        if post is not None:
-            post_arr = np.ascontiguousarray(post, np.int32) if not isinstance(post, bool) else np.zeros(
-                (B, self.code.n), np.int32)
-        be = np.zeros(B, np.int32) if bit_errors else None
-        tot = None if totals is None else np.ascontiguousarray(totals, np.int64)
-        _check(lib().fpldpc_decode_host(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok),
-                                        _ptr(post_arr), _ptr(be), _ptr(tot)))
-        out = {"hard": hard, "iters": iters, "syndrome_ok": ok}
-        if post_arr is not None:
-            out["post"] = post_arr
-        if be is not None:
-            out["bit_errors"] = be
-        if tot is not None:
-            out["totals"] = tot
-        return out
 
-    def ber_sim(self, snr, sigma, harvest=None, **kw):
-        """Ordered BER/FER simulation (fpldpc_ber_sim): the reference harness's frame loop, batched.
-        Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
-        patterns (fpldpc_ber_sim_harvest), the filled Harvest under the result's "harvest" key."""
-        if harvest is not None:
-            return _harvest_sim("fpldpc", [self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
-        p, keep = sim_params(snr, sigma, **kw)
-        r = SimResult()
-        _check(lib().fpldpc_ber_sim(self._h, ctypes.byref(p), ctypes.byref(r)))
-        del keep
-        return {k: getattr(r, k) for k, _ in SimResult._fields_}
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.fpldpc_decoder_destroy(self._h)
-            self._h = None
-
-
-class LayeredDecoder:
+class LayeredDecoder(_DecoderBase):
     """fpldpc_layered_t: the layered (row-serial) schedule of the fixed-point decoder, batched on the
     GPU.  layer_checks = 0 picks the layer size (Code.layering).  Same outputs as Decoder.
     post_bits / msg_bits (both 0: nothing saturated) give the saturated decoder of
@@ -473,10 +474,7 @@ class LayeredDecoder:
     The min-sum decoder takes every loadable code (n <= 65535, check degrees 2..64): where its state does
     not fit LDS it lives in global memory (describe: "mem=global ... scratch=<bytes>")."""
 
-    _abi = "fpldpc_layered"  # the entry points the shared methods below call (MinSumDecoder: fpldpc_minsum)
-
-    def _fn(self, name):
-        return getattr(lib(), f"{self._abi}_{name}")
+    _ENTRY = _entries("fpldpc_layered")
 
     def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
                  layer_checks=0, post_bits=0, msg_bits=0, check="sxor", scale_16=16, offset=0):
@@ -486,12 +484,7 @@ class LayeredDecoder:
             raise ValueError("check='minsum' needs post_bits and msg_bits")
         if check == "sxor" and (scale_16 != 16 or offset != 0):
             raise ValueError("scale_16 and offset belong to check='minsum'")
-        p = Params()
-        lib().fpldpc_params_default(ctypes.byref(p))
-        p.max_iter, p.frac_bits, p.width_mask = max_iter, frac_bits, width_mask
-        p.early_term, p.precheck, p.device = int(bool(early_term)), int(bool(precheck)), device
-        self.code = code
-        self.params = p
+        p = self._params(max_iter, frac_bits, width_mask, early_term, precheck, device)
         h = ctypes.c_void_p()
         if check == "minsum":
             _check(lib().fpldpc_layered_create_minsum(code._h, ctypes.byref(p), layer_checks, post_bits, msg_bits,
@@ -501,70 +494,7 @@ class LayeredDecoder:
         else:
             _check(lib().fpldpc_layered_create_sat(code._h, ctypes.byref(p), layer_checks, post_bits, msg_bits,
                                                    ctypes.byref(h)))
-        self._h = h
-        self.hard_words = (code.n + 31) // 32
-
-    def describe(self):
-        buf = ctypes.create_string_buffer(256)
-        _check(self._fn("describe")(self._h, buf, 256))
-        return buf.value.decode()
-
-    def set_reference(self, info_index, info_bits):
-        idx = np.ascontiguousarray(info_index, np.int32)
-        bits = np.ascontiguousarray(info_bits, np.uint8)
-        _check(self._fn("set_reference")(self._h, _ptr(idx), _ptr(bits), len(idx)))
-
-    def decode_ptrs(self, llr_ptr, llr_type, batch, hard=0, iters=0, syn_ok=0, post=0, bit_errors=0, totals=0,
-                    stream=0):
-        """Asynchronous decode on device pointers (ints); stream is a hipStream_t as int."""
-        c = ctypes.c_void_p
-        _check(self._fn("decode")(self._h, c(llr_ptr), llr_type, batch, c(hard or None), c(iters or None),
-                                  c(syn_ok or None), c(post or None), c(bit_errors or None), c(totals or None),
-                                  c(stream or None)))
-
-    decode_torch = Decoder.decode_torch  # the same tensor plumbing over this class's decode_ptrs
-
-    def decode_host(self, llr, post=None, bit_errors=False, totals=None):
-        """Synchronous decode of a host [B][n] int16/int32 array; returns numpy outputs (as Decoder.decode_host)."""
-        llr = np.ascontiguousarray(llr)
-        assert llr.ndim == 2 and llr.shape[1] == self.code.n and llr.dtype in (np.int16, np.int32)
-        B = llr.shape[0]
-        llr_type = FPLDPC_LLR_I16 if llr.dtype == np.int16 else FPLDPC_LLR_I32
-        hard = np.zeros((B, self.hard_words), np.uint32)
-        iters = np.zeros(B, np.int32)
-        ok = np.zeros(B, np.uint8)
-        post_arr = None
-        if post is not None:
-            post_arr = np.ascontiguousarray(post, np.int32) if not isinstance(post, bool) else np.zeros(
-                (B, self.code.n), np.int32)
-        be = np.zeros(B, np.int32) if bit_errors else None
-        tot = None if totals is None else np.ascontiguousarray(totals, np.int64)
-        _check(self._fn("decode_host")(self._h, _ptr(llr), llr_type, B, _ptr(hard), _ptr(iters), _ptr(ok), _ptr(post_arr),
-                                       _ptr(be), _ptr(tot)))
-        out = {"hard": hard, "iters": iters, "syndrome_ok": ok}
-        if post_arr is not None:
-            out["post"] = post_arr
-        if be is not None:
-            out["bit_errors"] = be
-        if tot is not None:
-            out["totals"] = tot
-        return out
-
-    def ber_sim(self, snr, sigma, harvest=None, **kw):
-        """Ordered BER/FER simulation around this decoder (fpldpc_layered_ber_sim / fpldpc_minsum_ber_sim), as
-        Decoder.ber_sim.  Keywords: see sim_params(); harvest as in Decoder.ber_sim."""
-        if harvest is not None:
-            return _harvest_sim(self._abi, [self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
-        p, keep = sim_params(snr, sigma, **kw)
-        r = SimResult()
-        _check(self._fn("ber_sim")(self._h, ctypes.byref(p), ctypes.byref(r)))
-        del keep
-        return {k: getattr(r, k) for k, _ in SimResult._fields_}
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            getattr(_lib, f"{self._abi}_destroy")(self._h)
-            self._h = None
+        self._adopt(code, h, p)
 
 
 class MinSumDecoder(LayeredDecoder):
@@ -574,19 +504,14 @@ class MinSumDecoder(LayeredDecoder):
     state and the accumulators do not fit LDS they live in global memory (describe: "mem=global ...
     scratch=<bytes>").  Same outputs and methods as Decoder / LayeredDecoder."""
 
-    _abi = "fpldpc_minsum"
+    _ENTRY = _entries("fpldpc_minsum")
 
     def __init__(self, code, max_iter=30, early_term=True, precheck=False, device=-1, post_bits=12, msg_bits=10,
                  scale_16=16, offset=0):
-        p = Params()
-        lib().fpldpc_params_default(ctypes.byref(p))
-        p.max_iter, p.early_term, p.precheck, p.device = max_iter, int(bool(early_term)), int(bool(precheck)), device
-        self.code = code
-        self.params = p
+        p = self._params(max_iter=max_iter, early_term=early_term, precheck=precheck, device=device)
         h = ctypes.c_void_p()
         _check(lib().fpldpc_minsum_create(code._h, ctypes.byref(p), post_bits, msg_bits, scale_16, offset, ctypes.byref(h)))
-        self._h = h
-        self.hard_words = (code.n + 31) // 32
+        self._adopt(code, h, p)
 
 
 class Encoder:
@@ -850,16 +775,16 @@ class Harvest:
             self._h = None
 
 
-def _harvest_sim(abi, decoders, snr, sigma, collective, harvest, kw):
-    """<abi>_ber_sim_harvest over `decoders`; harvest is a Harvest or max_records for a new one."""
+def _harvest_sim(decoders, snr, sigma, collective, harvest, kw):
+    """The decoders' <family>_ber_sim_harvest over them; harvest is a Harvest or max_records for a new one."""
     hv = harvest if isinstance(harvest, Harvest) else Harvest(decoders[0].code, int(harvest))
     p, keep = sim_params(snr, sigma, **kw)
     hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
     r = SimResult()
     used = ctypes.c_int32(0)
     hv._refresh()
-    _check(getattr(lib(), abi + "_ber_sim_harvest")(hs, len(decoders), ctypes.byref(p), collective, hv._h, ctypes.byref(r),
-                                                    ctypes.byref(used)))
+    _check(decoders[0]._fn("ber_sim_harvest")(hs, len(decoders), ctypes.byref(p), collective, hv._h, ctypes.byref(r),
+                                              ctypes.byref(used)))
     del keep
     out = {k: getattr(r, k) for k, _ in SimResult._fields_}
     out["harvest"] = hv
@@ -874,12 +799,11 @@ def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=Non
     kinds = {type(d) for d in decoders}
     if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
         raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
-    abi = {Decoder: "fpldpc", LayeredDecoder: "fpldpc_layered", MinSumDecoder: "fpldpc_minsum"}[kinds.pop()]
     if harvest is not None:
-        out, used = _harvest_sim(abi, decoders, snr, sigma, collective, harvest, kw)
+        out, used = _harvest_sim(decoders, snr, sigma, collective, harvest, kw)
         out["collective"] = used
         return out
-    fn = getattr(lib(), abi + "_ber_sim_multi")
+    fn = decoders[0]._fn("ber_sim_multi")
     p, keep = sim_params(snr, sigma, **kw)
     hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
     r = SimResult()

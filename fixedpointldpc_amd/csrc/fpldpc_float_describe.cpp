@@ -13,7 +13,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "fpldpc_float_state.hpp"
-#include "fpldpc_internal.hpp"
+#include "fpldpc_host.hpp"
 #include "fpldpc_testing.h"
 
 using namespace fpldpc;
@@ -39,10 +39,8 @@ extern "C" int fpldpc_testing_float_describe(void *decoder, char *buf, int32_t l
     if (!dec || !buf || len <= 0) return fail(FPLDPC_ERR_ARG, "null decoder or buffer");
     if (!dec->fl) {
         // the tables and the kernel choice are built by the first decode: one all-zero frame, no outputs
-        int prev = -1;
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dec->device >= 0 && dec->device != prev && hipSetDevice(dec->device) != hipSuccess)
-            return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
+        DeviceGuard g(dec->device);
+        if (!g.ok) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         double *llr = nullptr;
         const size_t bytes = sizeof(double) * (size_t)dec->code.n;
         hipError_t e = hipMalloc((void **)&llr, bytes);
@@ -54,7 +52,6 @@ extern "C" int fpldpc_testing_float_describe(void *decoder, char *buf, int32_t l
             if (e != hipSuccess) st = fail_hip((int)e, "float describe: first decode");
         }
         (void)hipFree(llr);
-        if (prev >= 0) (void)hipSetDevice(prev);
         if (st != FPLDPC_OK) return st;
     }
     const FloatState *s = dec->fl;

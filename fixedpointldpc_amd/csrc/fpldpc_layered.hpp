@@ -5,13 +5,16 @@
 // fpldpc_minsum_device.hpp the min-sum rule).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
-// c2v of every check persists across layers) and the flooding decoder's structs stay as the flooding
-// kernels were compiled against them.
+// c2v of every check persists across layers).  What every decoder object has, and the host plumbing around
+// it (creation checks, reference bits, the checks of a decode call, the staged host decode), is
+// fpldpc_host.hpp's DecoderCore, which this object is built on.  The flooding decoder's object
+// (fpldpc_internal.hpp) still carries its own copy of that state: the kernel build id hashes the units that
+// are compiled against its layout.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
-#include "fpldpc_internal.hpp"
+#include "fpldpc_host.hpp"
 
 namespace fpldpc {
 
@@ -96,10 +99,7 @@ hipError_t raise_dynamic_lds(const void *fn, size_t bytes);
 }  // namespace fpldpc
 
 // Layered decoder object (fpldpc_layered_t).
-struct fpldpc_layered {
-    fpldpc_code code;
-    fpldpc_params params{};
-    int device = 0;
+struct fpldpc_layered : fpldpc::DecoderCore {
     int L = 0, layers = 0;
     int post_bits = 0, msg_bits = 0;  // fpldpc_layered_create_sat / _minsum; 0: unsaturated
     int scale_16 = 16, offset = 0;    // fpldpc_layered_create_minsum
@@ -108,12 +108,6 @@ struct fpldpc_layered {
     uint8_t *d_cdeg = nullptr;
     int *d_counter = nullptr;
     void *d_scratch = nullptr;
-    int32_t *d_info_idx = nullptr;
-    uint8_t *d_info_bits = nullptr;
-    int k_info = 0;
-    hipStream_t stream = nullptr;  // fpldpc_layered_decode_host staging
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
 };
 
 // Flooding min-sum decoder object (fpldpc_minsum_t): a type of its own in the C ABI over the same plumbing.

@@ -58,12 +58,6 @@ using namespace fpldpc;
 
 namespace {
 
-#define SIM_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return fail_hip((int)_e, #expr); \
-    } while (0)
-
 // The decoder behind a rank or a slot: the six things the simulation asks of one, for fpldpc_decoder_t and
 // for fpldpc_layered_t (fpldpc_minsum_t enters as the layered object it wraps).
 struct Dec {
@@ -170,25 +164,25 @@ struct Rank {
             int st = dec.create_twin(&twin);
             if (st) return st;
             s[1].dec = twin;
-            SIM_TRY(hipStreamCreateWithFlags(&xs, hipStreamNonBlocking));
+            HIP_TRY(hipStreamCreateWithFlags(&xs, hipStreamNonBlocking));
         }
         for (auto &x : s) {
-            if (!sp->device_channel) SIM_TRY(hipHostMalloc((void **)&x.h_llr, llr_bytes, hipHostMallocDefault));
-            SIM_TRY(hipHostMalloc((void **)&x.h_out, ((size_t)chunk * 2 + 1) * sizeof(int32_t), hipHostMallocDefault));
-            SIM_TRY(hipMalloc((void **)&x.d_llr, llr_bytes));
-            SIM_TRY(hipMalloc((void **)&x.d_out, ((size_t)chunk * 2 + 1) * sizeof(int32_t)));
-            SIM_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+            if (!sp->device_channel) HIP_TRY(hipHostMalloc((void **)&x.h_llr, llr_bytes, hipHostMallocDefault));
+            HIP_TRY(hipHostMalloc((void **)&x.h_out, ((size_t)chunk * 2 + 1) * sizeof(int32_t), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&x.d_llr, llr_bytes));
+            HIP_TRY(hipMalloc((void **)&x.d_out, ((size_t)chunk * 2 + 1) * sizeof(int32_t)));
+            HIP_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
         }
         if (sp->device_channel) {
             if (sp->codeword) {
-                SIM_TRY(hipMalloc((void **)&d_forced, sizeof(int32_t) * std::max(sp->n_forced, 0) + n));
+                HIP_TRY(hipMalloc((void **)&d_forced, sizeof(int32_t) * std::max(sp->n_forced, 0) + n));
                 d_cw = reinterpret_cast<const uint8_t *>(d_forced + std::max(sp->n_forced, 0));
-                SIM_TRY(hipMemcpy((void *)d_cw, sp->codeword, n, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy((void *)d_cw, sp->codeword, n, hipMemcpyHostToDevice));
             } else if (sp->n_forced > 0) {
-                SIM_TRY(hipMalloc((void **)&d_forced, sizeof(int32_t) * sp->n_forced));
+                HIP_TRY(hipMalloc((void **)&d_forced, sizeof(int32_t) * sp->n_forced));
             }
             if (sp->n_forced > 0)
-                SIM_TRY(hipMemcpy(d_forced, sp->forced_index, sizeof(int32_t) * sp->n_forced, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(d_forced, sp->forced_index, sizeof(int32_t) * sp->n_forced, hipMemcpyHostToDevice));
         }
         if (hv) {
             int st = setup_harvest();
@@ -211,15 +205,15 @@ struct Rank {
             if (st) return st;
             k = x.enc->k;
             if (k < 1) return fail(FPLDPC_ERR_ARG, "random_info: the code has no information bits");
-            SIM_TRY(hipMalloc((void **)&x.d_info, (size_t)chunk * k));
-            SIM_TRY(hipMalloc((void **)&x.d_cw, (size_t)chunk * n));
-            if (!x.d_hard) SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hw * sizeof(uint32_t)));
-            SIM_TRY(hipMemsetAsync(x.d_info, 0, (size_t)chunk * k, x.dec.stream()));
+            HIP_TRY(hipMalloc((void **)&x.d_info, (size_t)chunk * k));
+            HIP_TRY(hipMalloc((void **)&x.d_cw, (size_t)chunk * n));
+            if (!x.d_hard) HIP_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hw * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(x.d_info, 0, (size_t)chunk * k, x.dec.stream()));
             if ((st = fpldpc_encoder_encode(x.enc, x.d_info, chunk, x.d_cw, x.dec.stream()))) return st;
-            SIM_TRY(hipStreamSynchronize(x.dec.stream()));
+            HIP_TRY(hipStreamSynchronize(x.dec.stream()));
         }
-        SIM_TRY(hipMalloc((void **)&d_info_idx, sizeof(int32_t) * k));
-        SIM_TRY(hipMemcpy(d_info_idx, s[0].enc->info_index.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc((void **)&d_info_idx, sizeof(int32_t) * k));
+        HIP_TRY(hipMemcpy(d_info_idx, s[0].enc->info_index.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice));
         return FPLDPC_OK;
     }
     // harvest: this device's check table, per slot the hard decisions (random_info or not) and the buffers of
@@ -230,17 +224,17 @@ struct Rank {
         cap = std::min(hv->max_records, chunk);
         row_words = hv->hard_words + hv->syn_words;
         if (sp->codeword && !sp->device_channel) {
-            SIM_TRY(hipMalloc((void **)&d_hv_cw, n));
-            SIM_TRY(hipMemcpy(d_hv_cw, sp->codeword, n, hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc((void **)&d_hv_cw, n));
+            HIP_TRY(hipMemcpy(d_hv_cw, sp->codeword, n, hipMemcpyHostToDevice));
         }
         for (auto &x : s) {
-            SIM_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hv->hard_words * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&x.d_hard, (size_t)chunk * hv->hard_words * sizeof(uint32_t)));
             const size_t block = ((size_t)chunk * 2 + (size_t)cap * row_words) * sizeof(int32_t);
-            SIM_TRY(hipMalloc((void **)&x.d_hv, block));
-            SIM_TRY(hipHostMalloc((void **)&x.h_hv, block, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&x.d_hv, block));
+            HIP_TRY(hipHostMalloc((void **)&x.h_hv, block, hipHostMallocDefault));
             if (cap > 0) {
-                SIM_TRY(hipMalloc((void **)&x.d_rows, (size_t)chunk * row_words * sizeof(uint32_t)));
-                SIM_TRY(hipMalloc((void **)&x.d_pos, (size_t)chunk * sizeof(int32_t)));
+                HIP_TRY(hipMalloc((void **)&x.d_rows, (size_t)chunk * row_words * sizeof(uint32_t)));
+                HIP_TRY(hipMalloc((void **)&x.d_pos, (size_t)chunk * sizeof(int32_t)));
             }
         }
         return FPLDPC_OK;
@@ -263,7 +257,7 @@ struct Rank {
                 return r;
             words += (size_t)c * row_words;
         }
-        SIM_TRY(hipMemcpyAsync(x.h_hv, x.d_hv, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(x.h_hv, x.d_hv, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         return FPLDPC_OK;
     }
     // Host channel: the chunk's LLRs on host threads (device channel: in submit).
@@ -285,7 +279,7 @@ struct Rank {
         const bool count_bits = sp->count_mode == FPLDPC_COUNT_BITS;
         if (sp->device_channel) {
             int32_t *ovf = x.d_out + 2 * (size_t)chunk;
-            SIM_TRY(hipMemsetAsync(ovf, 0, sizeof(int32_t), st));
+            HIP_TRY(hipMemsetAsync(ovf, 0, sizeof(int32_t), st));
             if (sp->random_info) {  // this chunk's information bits and their codewords, a codeword per frame
                 if ((r = fpldpc_info_bits(sp->info_seed, x.first, (int32_t)x.frames, k, x.d_info, st))) return r;
                 if ((r = fpldpc_encoder_encode(x.enc, x.d_info, (int32_t)x.frames, x.d_cw, st))) return r;
@@ -297,9 +291,9 @@ struct Rank {
             if (sp->n_forced > 0 &&
                 (r = launch_force_llr(x.d_llr, (int)x.frames, n, d_forced, sp->n_forced, (int16_t)sp->forced_llr, st)))
                 return r;
-            SIM_TRY(hipMemcpyAsync(x.h_out + 2 * (size_t)chunk, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(x.h_out + 2 * (size_t)chunk, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         } else {
-            SIM_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * sizeof(int16_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * sizeof(int16_t), hipMemcpyHostToDevice, st));
         }
         // random_info: the decoder has no reference; its hard decisions are counted against the chunk's own bits
         r = x.dec.decode(x.d_llr, (int32_t)x.frames, sp->random_info || hv ? x.d_hard : nullptr, x.d_out + chunk,
@@ -310,15 +304,15 @@ struct Rank {
             return r;
         if (hv && (r = submit_harvest(x, st))) return r;
         if (count_bits)
-            SIM_TRY(hipMemcpyAsync(x.h_out, x.d_out, (size_t)x.frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        SIM_TRY(hipMemcpyAsync(x.h_out + chunk, x.d_out + chunk, (size_t)x.frames * sizeof(int32_t),
+            HIP_TRY(hipMemcpyAsync(x.h_out, x.d_out, (size_t)x.frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(x.h_out + chunk, x.d_out + chunk, (size_t)x.frames * sizeof(int32_t),
                                hipMemcpyDeviceToHost, st));
-        SIM_TRY(hipEventRecord(x.done, st));
+        HIP_TRY(hipEventRecord(x.done, st));
         return FPLDPC_OK;
     }
     int wait(Slot &x) {
         if (x.frames <= 0) return FPLDPC_OK;
-        SIM_TRY(hipEventSynchronize(x.done));
+        HIP_TRY(hipEventSynchronize(x.done));
         if (sp->device_channel && x.h_out[2 * (size_t)chunk] != 0)
             return fail(FPLDPC_ERR_ARG, "LLR does not fit int16");  // as the host channel
         decoded += x.frames;
@@ -406,7 +400,7 @@ struct Exchange {
         dbuf.assign(ndev, nullptr);
         for (int i = 0; i < ndev; ++i) {
             if (hipSetDevice(devs[i]) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice");
-            SIM_TRY(hipMalloc((void **)&dbuf[i], sizeof(int64_t) * kWords * (ndev + 1)));
+            HIP_TRY(hipMalloc((void **)&dbuf[i], sizeof(int64_t) * kWords * (ndev + 1)));
         }
         return FPLDPC_OK;
     }
@@ -429,10 +423,10 @@ struct Exchange {
         if (aborted) return fail(FPLDPC_ERR_HIP, "another rank of the simulation failed");
         if (rccl) {
             int64_t *send = dbuf[rank], *recv = dbuf[rank] + kWords;
-            SIM_TRY(hipMemcpyAsync(send, mine, sizeof(int64_t) * kWords, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(send, mine, sizeof(int64_t) * kWords, hipMemcpyHostToDevice, st));
             ncclResult_t r = ncclAllGather(send, recv, kWords, ncclInt64, comms[rank], st);
             if (r != ncclSuccess) return fail(FPLDPC_ERR_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(r));
-            SIM_TRY(hipMemcpyAsync(all, recv, sizeof(int64_t) * kWords * ndev, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(all, recv, sizeof(int64_t) * kWords * ndev, hipMemcpyDeviceToHost, st));
             return sync(rank, st);
         }
         int64_t *buf = &slots[(size_t)(calls[rank]++ & 1) * ndev * kWords];
@@ -446,10 +440,10 @@ struct Exchange {
         if (aborted) return fail(FPLDPC_ERR_HIP, "another rank of the simulation failed");
         if (rccl) {
             int64_t *buf = dbuf[rank];
-            SIM_TRY(hipMemcpyAsync(buf, mine, sizeof(int64_t) * kWords, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(buf, mine, sizeof(int64_t) * kWords, hipMemcpyHostToDevice, st));
             ncclResult_t r = ncclAllReduce(buf, buf, kWords, ncclInt64, ncclSum, comms[rank], st);
             if (r != ncclSuccess) return fail(FPLDPC_ERR_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-            SIM_TRY(hipMemcpyAsync(sum, buf, sizeof(int64_t) * kWords, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(sum, buf, sizeof(int64_t) * kWords, hipMemcpyDeviceToHost, st));
             return sync(rank, st);
         }
         std::vector<int64_t> all((size_t)ndev * kWords);
@@ -610,8 +604,8 @@ int rank_loop(Shared &sh, int rank) {
     total.add(unpack(red));
     // drain: a generated-but-not-submitted slot holds nothing on the device; a submitted one (two
     // chunks in flight, decoded past the stop frame) is waited for, not counted
-    for (const Slot &z : R.s) SIM_TRY(hipStreamSynchronize(z.dec.stream()));
-    SIM_TRY(hipStreamSynchronize(st));
+    for (const Slot &z : R.s) HIP_TRY(hipStreamSynchronize(z.dec.stream()));
+    HIP_TRY(hipStreamSynchronize(st));
     if (rank == 0) {
         sh.result = total;
         sh.decoded = red[4];
@@ -646,14 +640,6 @@ int validate(const Dec &dec, const fpldpc_sim_params *sp) {
     return FPLDPC_OK;
 }
 
-struct DeviceRestore {
-    int d = -1;
-    DeviceRestore() { (void)hipGetDevice(&d); }
-    ~DeviceRestore() {
-        if (d >= 0) (void)hipSetDevice(d);
-    }
-};
-
 // hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error
 int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used,
             fpldpc_harvest *hv = nullptr, bool harvesting = false) {
@@ -687,7 +673,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
                       (collective == FPLDPC_COLL_AUTO && ndev == 1 && g_inject.comm_init.load() == 2);
     if (rccl && !distinct) return fail(FPLDPC_ERR_ARG, "RCCL needs the decoders on distinct devices");
     const auto t0 = std::chrono::steady_clock::now();
-    DeviceRestore restore;
+    DeviceGuard restore(-1);  // the ranks below set their own devices: the caller gets its own back
     const char *ov = getenv("FPLDPC_SIM_OVERLAP");
     const bool overlap = !(ov && *ov == '0');
 

@@ -1,0 +1,105 @@
+"""The host form of every decoder (fpldpc_decode_host, fpldpc_layered_decode_host for the unsaturated and the
+min-sum decoder, fpldpc_minsum_decode_host, fpldpc_decode_float_host) with every subset of its six optional
+outputs, through the library itself: the Python wrappers always pass hard, iters and syndrome_ok.
+
+Array code p = 13, r = 3 (n = 169: six hard words, no buffer a multiple of 256 bytes; m = 39), 5 iterations (float:
+3).  One decoder object per kind decodes batches of 3, 300 and 2 frames in that order, so that its staging block
+grows and a larger block is then reused.  Within a batch every output a call asks for equals the same output of
+the call that asks for all six on the same LLRs, and the totals add up across the calls from the caller's
+starting values.  The fixed-point decoders run with the pre-check and a noiseless first frame, whose seeded
+posteriors come back untouched.  Without reference bits a call that asks for bit_errors fails with its own
+family's text."""
+import ctypes
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+P, R, N, HW = 13, 3, 169, 6
+BATCHES = (3, 300, 2)
+OUTS = ("hard", "iters", "syndrome_ok", "post", "bit_errors", "totals")
+TOT0 = np.array([5, 70, 900, 11000], np.int64)
+
+# kind: (decoder, entry point, LLR dtypes, the set_reference its error text names)
+KINDS = {
+    "flood": (lambda F, c: F.Decoder(c, max_iter=5, precheck=True), "fpldpc_decode_host", (np.int16, np.int32),
+              "fpldpc_set_reference"),
+    "layered": (lambda F, c: F.LayeredDecoder(c, max_iter=5, precheck=True), "fpldpc_layered_decode_host",
+                (np.int16, np.int32), "fpldpc_layered_set_reference"),
+    "layered-minsum": (lambda F, c: F.LayeredDecoder(c, max_iter=5, precheck=True, post_bits=12, msg_bits=10, check="minsum"),
+                       "fpldpc_layered_decode_host", (np.int16, np.int32), "fpldpc_layered_set_reference"),
+    "minsum": (lambda F, c: F.MinSumDecoder(c, max_iter=5, precheck=True), "fpldpc_minsum_decode_host",
+               (np.int16, np.int32), "fpldpc_minsum_set_reference"),
+    "float": (lambda F, c: F.Decoder(c, max_iter=3), "fpldpc_decode_float_host", (np.float64,), "fpldpc_set_reference"),
+}
+
+
+@pytest.fixture(scope="module")
+def setup(F):
+    code = F.Code.array(P, R)
+    assert (code.n, code.m) == (N, 39)
+    snr, sigma = F.snr_sigma(3.0, code.rate)
+    llr = F.channel_llr(20261021, 0, max(BATCHES), N, snr, sigma, dtype=np.int16)
+    llr[0] = 40  # noiseless all-zero codeword: the pre-check passes
+    return code, llr, F.Encoder.from_code(code).info_index
+
+
+def _llr(llr16, B, dt):
+    """The first B frames as int16 / int32 fixed-point LLRs (4 fraction bits) or as float64 LLRs."""
+    return np.ascontiguousarray(llr16[:B] / 16.0 if dt == np.float64 else llr16[:B], dt)
+
+
+def _call(F, dec, entry, llr, bufs):
+    ptr = [None if b is None else b.ctypes.data_as(ctypes.c_void_p) for b in bufs]
+    args = [dec._h, llr.ctypes.data_as(ctypes.c_void_p)]
+    if llr.dtype != np.float64:
+        args.append(F.FPLDPC_LLR_I16 if llr.dtype == np.int16 else F.FPLDPC_LLR_I32)
+    return getattr(F.lib(), entry)(*args, llr.shape[0], *ptr)
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_every_output_subset(F, setup, kind):
+    code, llr16, info_index = setup
+    make, entry, dtypes, ref_name = KINDS[kind]
+    dec = make(F, code)
+    fixed = kind != "float"
+    post_t = np.int32 if fixed else np.float64
+    # bit_errors without reference bits: the family's own text, whatever else is asked for
+    be = np.zeros(3, np.int32)
+    assert _call(F, dec, entry, _llr(llr16, 3, dtypes[0]), [None, None, None, None, be, None]) == -1
+    assert F.lib().fpldpc_last_error().decode().endswith("bit_errors requested without " + ref_name)
+    dec.set_reference(info_index, np.zeros(len(info_index), np.uint8))
+    for dt in dtypes:
+        for B in BATCHES:
+            llr = _llr(llr16, B, dt)
+            seed = (np.arange(B * N).reshape(B, N) % 251 - 125).astype(post_t)
+            running, after, got = TOT0.copy(), {}, {}
+            for mask in range(64):  # 63, the last, asks for everything
+                want = [bool(mask >> i & 1) for i in range(6)]
+                bufs = [np.full((B, HW), 0xA5A5A5A5, np.uint32), np.full(B, -7, np.int32), np.full(B, 9, np.uint8), seed.copy(),
+                        np.full(B, -3, np.int32), running]
+                bufs = [b if w else None for b, w in zip(bufs, want)]
+                assert _call(F, dec, entry, llr, bufs) == 0, (mask, F.lib().fpldpc_last_error().decode())
+                got[mask] = bufs
+                if want[5]:
+                    after[mask] = running.copy()
+            full = dict(zip(OUTS, got[63]))
+            where = f"{kind} {np.dtype(dt).name} batch {B}"
+            # the all-outputs call itself: totals are this batch's sums on top of the 31 calls before it
+            delta = np.array([full["bit_errors"].sum(), (full["bit_errors"] > 0).sum(), B, full["iters"].sum()], np.int64)
+            assert (full["iters"] >= 0).all() and (full["iters"] <= (5 if fixed else 3)).all(), where
+            assert set(np.unique(full["syndrome_ok"])) <= {0, 1} and full["syndrome_ok"][0] == 1, where
+            assert not (full["hard"][0] != 0).any(), where
+            assert (full["post"][1:] != seed[1:]).any(), where
+            if fixed:  # frame 0 passes the pre-check: its seeded posteriors stay
+                assert (full["post"][0] == seed[0]).all(), where
+            calls = 0
+            for mask in range(64):
+                for name, b in zip(OUTS[:5], got[mask][:5]):
+                    if b is not None:
+                        assert np.array_equal(b, full[name]), f"{where}: {name} of subset {mask:06b}"
+                if mask in after:
+                    calls += 1
+                    assert np.array_equal(after[mask], TOT0 + calls * delta), f"{where}: totals after subset {mask:06b}"
+            assert calls == 32

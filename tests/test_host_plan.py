@@ -1,0 +1,25 @@
+"""The decoders' host staging layout and slot-major index table (fpldpc_host_plan.hpp, used by the staged host
+decode and the decoders' table upload) on the CPU, against their definitions restated in
+tests/cpp/host_plan_test.cpp: 20000 random layouts (alignment, disjoint regions in bounds, the fixed-point
+decoders' long-standing offsets when every output is wanted) and 300 random irregular codes (pitch m and m
+rounded up to 64, the code's own order and a stable sort by degree).  Built a second time with the address and
+undefined-behaviour sanitizers."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],
+                         ids=["plain", "sanitized"])
+def test_layout_and_table(tmp_path, flags):
+    exe = str(tmp_path / "host_plan_test")
+    subprocess.run(["g++", "-std=c++17", *flags, "-I", os.path.join(ROOT, "fixedpointldpc_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "cpp", "host_plan_test.cpp")], check=True, timeout=300)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert " 0 mismatches" in p.stdout
