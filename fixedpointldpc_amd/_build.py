@@ -26,6 +26,9 @@ SOURCES = [
     # the host plumbing the decoder objects share (guard, creation checks, reference bits, staged host decode): no
     # kernel reads it and it launches none, so it stays outside the build id
     "fpldpc_host.cpp",
+    # the flooding decoder's entry points that read the object or stage host buffers (describe, counts, the host
+    # decodes): they go through fpldpc_decode / fpldpc_decode_float to reach a kernel, outside the build id too
+    "fpldpc_decoder_api.cpp",
     # the layered decoder: not in DEVICE_TUS / HASHED_TUS -- the build id covers the kernels with committed counters
     "fpldpc_layered.cpp",
     "fpldpc_layered.hip",
@@ -54,9 +57,9 @@ DEVICE_TUS = ["fpldpc_kernels.hip", "fpldpc_kernels_a1.hip", "fpldpc_kernels_w1.
 SOURCE_FLAGS = {"fpldpc_kernels_a1.hip": ["-Xarch_device", "-mllvm=-disable-post-ra", "-Xarch_device", "-mllvm=-misched=ilpmax"],
                 "fpldpc_kernels.hip": ["-Xarch_device", "-mllvm=-amdgpu-use-amdgpu-trackers"],
                 "fpldpc_kernels_w1.hip": ["-Xarch_device", "-mllvm=-disable-post-ra"]}
-# + the tables and launch arguments the kernels read.  fpldpc_decoder.cpp and the host tail of fpldpc_float.hip still
-# hold the flooding decoder's own staging, reference upload and describe, so an edit to those moves the id as well;
-# the layered and min-sum decoders' plumbing is fpldpc_host.cpp's, outside it.
+# + fpldpc_decoder.cpp: the tables the flooding kernels read, the reference mask and the launch arguments.  Staging,
+# describe and the other entry points around a decode are fpldpc_decoder_api.cpp's and fpldpc_host.cpp's, outside the
+# id: an edit there leaves the committed counters valid.
 HASHED_TUS = DEVICE_TUS + ["fpldpc_decoder.cpp"]
 _PROBED = {}
 

@@ -29,7 +29,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "fpldpc_internal.hpp"
+#include "fpldpc_host.hpp"
 #include "fpldpc_float_math.hpp"
 #include "fpldpc_float_state.hpp"
 
@@ -804,12 +804,6 @@ __global__ void __launch_bounds__(kFT) bp_float_kernel(FArgs a) {
     }
 }
 
-#define F_TRY(expr)                                            \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return fail_hip((int)_e, #expr); \
-    } while (0)
-
 int float_setup(fpldpc_decoder *dec) {
     if (dec->fl) return FPLDPC_OK;
     const fpldpc_code &H = dec->code;
@@ -849,41 +843,29 @@ int float_setup(fpldpc_decoder *dec) {
         }
     }
     hipDeviceProp_t prop;
-    F_TRY(hipGetDeviceProperties(&prop, dec->device));
+    HIP_TRY(hipGetDeviceProperties(&prop, dec->device));
     s->lds = sizeof(double) * (size_t)n;
-    if (s->lds > 64 * 1024) F_TRY(hipFuncSetAttribute((const void *)s->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
+    if (s->lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)s->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
     int per_cu = 0;
-    F_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)s->fn, kFT, s->lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)s->fn, kFT, s->lds));
     if (per_cu < 1) return fail(FPLDPC_ERR_UNSUPPORTED, "float decoder: kernel does not fit a CU");
     // Diagnostic: FPLDPC_FLOAT_WG_PER_CU=k caps the persistent grid (the edge scratch is per workgroup)
     if (const char *g = getenv("FPLDPC_FLOAT_WG_PER_CU"))
         if (atoi(g) > 0) per_cu = std::min(per_cu, atoi(g));
     s->grid = per_cu * prop.multiProcessorCount;
-    F_TRY(hipMalloc(&s->d_cvar, sizeof(int32_t) * cvar.size()));
-    F_TRY(hipMalloc(&s->d_cdeg, m));
-    F_TRY(hipMalloc(&s->d_vedge, sizeof(int32_t) * std::max<size_t>(vedge.size(), 1)));
-    F_TRY(hipMalloc(&s->d_vdeg, n));
-    F_TRY(hipMalloc(&s->d_msg, sizeof(double) * s->planes * (size_t)s->grid * dc * m));
-    F_TRY(hipMalloc(&s->d_counter, sizeof(int)));
-    F_TRY(hipMemcpy(s->d_cvar, cvar.data(), sizeof(int32_t) * cvar.size(), hipMemcpyHostToDevice));
-    F_TRY(hipMemcpy(s->d_cdeg, cdeg.data(), m, hipMemcpyHostToDevice));
-    F_TRY(hipMemcpy(s->d_vedge, vedge.data(), sizeof(int32_t) * vedge.size(), hipMemcpyHostToDevice));
-    F_TRY(hipMemcpy(s->d_vdeg, vdeg.data(), n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s->d_cvar, sizeof(int32_t) * cvar.size()));
+    HIP_TRY(hipMalloc(&s->d_cdeg, m));
+    HIP_TRY(hipMalloc(&s->d_vedge, sizeof(int32_t) * std::max<size_t>(vedge.size(), 1)));
+    HIP_TRY(hipMalloc(&s->d_vdeg, n));
+    HIP_TRY(hipMalloc(&s->d_msg, sizeof(double) * s->planes * (size_t)s->grid * dc * m));
+    HIP_TRY(hipMalloc(&s->d_counter, sizeof(int)));
+    HIP_TRY(hipMemcpy(s->d_cvar, cvar.data(), sizeof(int32_t) * cvar.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_cdeg, cdeg.data(), m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_vedge, vedge.data(), sizeof(int32_t) * vedge.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_vdeg, vdeg.data(), n, hipMemcpyHostToDevice));
     dec->fl = s.release();
     return FPLDPC_OK;
 }
-
-struct Guard {
-    int prev = -1;
-    bool ok = true;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~Guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 }  // namespace fpldpc
@@ -894,18 +876,15 @@ extern "C" {
 
 int fpldpc_decode_float(fpldpc_decoder_t dec, const double *llr, int32_t batch, uint32_t *hard, int32_t *iters,
                         uint8_t *syndrome_ok, double *post, int32_t *bit_errors, int64_t *totals, void *stream) {
-    if (!dec) return fail(FPLDPC_ERR_ARG, "null decoder");
-    if (batch < 0) return fail(FPLDPC_ERR_ARG, "negative batch");
-    if (batch == 0) return FPLDPC_OK;
-    if (!llr) return fail(FPLDPC_ERR_ARG, "null llr");
-    if (bit_errors && dec->k_info == 0) return fail(FPLDPC_ERR_ARG, "bit_errors requested without fpldpc_set_reference");
-    Guard g(dec->device);
-    if (!g.ok) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
-    int st = float_setup(dec);
+    DeviceGuard g;
+    bool run = false;
+    int st = decode_prologue(dec, llr, nullptr, batch, bit_errors, "fpldpc_set_reference", &g, &run);
+    if (st || !run) return st;
+    st = float_setup(dec);
     if (st) return st;
     FloatState *s = dec->fl;
     hipStream_t hs = (hipStream_t)stream;
-    F_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(int), hs));
+    HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(int), hs));
     FArgs a{};
     a.llr = llr;
     a.batch = batch;
@@ -933,47 +912,7 @@ int fpldpc_decode_float(fpldpc_decoder_t dec, const double *llr, int32_t batch, 
     a.k_info = dec->k_info;
     const int grid = std::min(s->grid, batch);
     hipLaunchKernelGGL(reinterpret_cast<void (*)(FArgs)>(const_cast<void *>(s->fn)), dim3(grid), dim3(kFT), s->lds, hs, a);
-    F_TRY(hipGetLastError());
-    return FPLDPC_OK;
-}
-
-int fpldpc_decode_float_host(fpldpc_decoder_t dec, const double *llr, int32_t batch, uint32_t *hard, int32_t *iters,
-                             uint8_t *syndrome_ok, double *post, int32_t *bit_errors, int64_t *totals) {
-    if (!dec) return fail(FPLDPC_ERR_ARG, "null decoder");
-    if (batch < 0) return fail(FPLDPC_ERR_ARG, "negative batch");
-    if (batch == 0) return FPLDPC_OK;
-    if (!llr) return fail(FPLDPC_ERR_ARG, "null llr");
-    Guard g(dec->device);
-    if (!g.ok) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
-    const size_t n = dec->code.n, B = batch, hw = (n + 31) / 32;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_llr = 0, o_hard = al(B * n * 8), o_it = o_hard + al(B * hw * 4), o_ok = o_it + al(B * 4),
-                 o_post = o_ok + al(B), o_be = o_post + al(post ? B * n * 8 : 0), o_tot = o_be + al(B * 4),
-                 total = o_tot + 64;
-    char *d = nullptr;
-    F_TRY(hipMalloc((void **)&d, total));
-    struct Free {
-        char *p;
-        ~Free() { (void)hipFree(p); }
-    } fr{d};
-    hipStream_t hs = nullptr;
-    F_TRY(hipMemcpy(d + o_llr, llr, B * n * 8, hipMemcpyHostToDevice));
-    int64_t *d_tot = totals ? reinterpret_cast<int64_t *>(d + o_tot) : nullptr;
-    if (totals) F_TRY(hipMemcpy(d_tot, totals, 32, hipMemcpyHostToDevice));
-    int st = fpldpc_decode_float(dec, reinterpret_cast<const double *>(d + o_llr), batch,
-                                 hard ? reinterpret_cast<uint32_t *>(d + o_hard) : nullptr,
-                                 iters ? reinterpret_cast<int32_t *>(d + o_it) : nullptr,
-                                 syndrome_ok ? reinterpret_cast<uint8_t *>(d + o_ok) : nullptr,
-                                 post ? reinterpret_cast<double *>(d + o_post) : nullptr,
-                                 bit_errors ? reinterpret_cast<int32_t *>(d + o_be) : nullptr, d_tot, hs);
-    if (st) return st;
-    F_TRY(hipDeviceSynchronize());
-    if (hard) F_TRY(hipMemcpy(hard, d + o_hard, B * hw * 4, hipMemcpyDeviceToHost));
-    if (iters) F_TRY(hipMemcpy(iters, d + o_it, B * 4, hipMemcpyDeviceToHost));
-    if (syndrome_ok) F_TRY(hipMemcpy(syndrome_ok, d + o_ok, B, hipMemcpyDeviceToHost));
-    if (post) F_TRY(hipMemcpy(post, d + o_post, B * n * 8, hipMemcpyDeviceToHost));
-    if (bit_errors) F_TRY(hipMemcpy(bit_errors, d + o_be, B * 4, hipMemcpyDeviceToHost));
-    if (totals) F_TRY(hipMemcpy(totals, d_tot, 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
     return FPLDPC_OK;
 }
 

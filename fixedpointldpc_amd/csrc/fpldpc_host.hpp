@@ -1,6 +1,7 @@
 // fpldpc_host.hpp -- the host plumbing every decoder object shares (fpldpc_host.cpp): the device guard, the
-// HIP-error-to-status macro, the parameter and device checks of creation, the state every decoder object has
-// (DecoderCore) with its reference bits, the checks every decode call starts with and the staged host decode.
+// HIP-error-to-status macro, the parameter and device checks of creation, the reference bits of the state every
+// decoder object has (DecoderCore, fpldpc_internal.hpp), the checks every decode call starts with and the staged
+// host decode.
 //
 // Outside the kernel build id (fixedpointldpc_amd/_build.py HASHED_TUS): nothing here is read by a kernel or
 // decides how one is chosen or launched.
@@ -49,20 +50,7 @@ int resolve_params(const fpldpc_params *params, fpldpc_params *p);
 // path) and for an ordinal the machine does not have.
 int select_device(int requested, int *dev);
 
-// What every decoder object has.  The decoder's own stream serves the staged host decode and the simulation.
-struct DecoderCore {
-    fpldpc_code code;
-    fpldpc_params params{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int32_t *d_info_idx = nullptr;  // reference bits (set_reference): positions [k_info] and bits [k_info]
-    uint8_t *d_info_bits = nullptr;
-    int k_info = 0;
-    void *d_stage = nullptr;  // staged_decode's block, grown to the largest call seen
-    size_t stage_bytes = 0;
-};
-
-// Frees what the core owns (on the decoder's device: the caller holds the guard).
+// Frees what the core (DecoderCore, fpldpc_internal.hpp) owns (on the decoder's device: the caller holds the guard).
 void core_free(DecoderCore &core);
 // Uploads (k > 0) or drops (k == 0) the reference bits; FPLDPC_ERR_ARG "bad reference" for a null core.
 int set_reference(DecoderCore *core, const int32_t *info_index, const uint8_t *info_bits, int32_t k);

@@ -1,6 +1,7 @@
-// fpldpc_host_plan.hpp -- the layout of a decoder's host staging block and the slot-major index table
-// of a code, as the decoders' host plumbing (fpldpc_host.cpp) uses them.  Header-only, no HIP: the CPU
-// test tests/cpp/host_plan_test.cpp checks both against their definitions restated there.
+// fpldpc_host_plan.hpp -- the layout of a decoder's host staging block, the slot-major index table of a
+// code and the packed reference mask, as the decoders' host code (fpldpc_host.cpp, fpldpc_layered.cpp,
+// fpldpc_decoder.cpp) uses them.  Header-only, no HIP: the CPU test tests/cpp/host_plan_test.cpp checks
+// each against its definition restated there.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -61,6 +62,22 @@ inline SlotTable slot_table(int m, int dc_max, const int32_t *cdeg, const int32_
         for (int k = 0; k < cdeg[r]; k++) t.vidx[(size_t)k * pitch + j] = (uint16_t)clist[(size_t)r * dc_max + k];
     }
     return t;
+}
+
+// The reference bits of k positions in a code of n variables as [2][ceil(n / 32)] words, the form the packed
+// kernels count bit errors from their hard-decision words with: bit v of the first half is set for every
+// position v, bit v of the second half is bit 0 of that position's reference bit.  Empty when a position
+// repeats (the index form counts such a position once per occurrence; a mask cannot).
+inline std::vector<uint32_t> reference_mask(int n, const int32_t *info_index, const uint8_t *info_bits, int k) {
+    const size_t hw = ((size_t)n + 31) / 32;
+    std::vector<uint32_t> mk(2 * hw, 0);
+    for (int i = 0; i < k; i++) {
+        const int v = info_index[i];
+        if (mk[v / 32] >> (v % 32) & 1) return {};
+        mk[v / 32] |= 1u << (v % 32);
+        mk[hw + v / 32] |= (uint32_t)(info_bits[i] & 1) << (v % 32);
+    }
+    return mk;
 }
 
 }  // namespace plan

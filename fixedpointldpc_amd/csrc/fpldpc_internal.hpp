@@ -25,6 +25,20 @@ struct fpldpc_code {
 
 namespace fpldpc {
 
+// What every decoder object has (the plumbing around it: fpldpc_host.hpp).  The decoder's own stream serves
+// the staged host decode and the simulation.
+struct DecoderCore {
+    fpldpc_code code;
+    fpldpc_params params{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int32_t *d_info_idx = nullptr;  // reference bits (set_reference): positions [k_info] and bits [k_info]
+    uint8_t *d_info_bits = nullptr;
+    int k_info = 0;
+    void *d_stage = nullptr;  // staged_decode's block, grown to the largest call seen
+    size_t stage_bytes = 0;
+};
+
 // Thread-local last-error plumbing for the C ABI.
 int fail(int code, const std::string &msg);
 int fail_hip(int hip_status, const char *what);
@@ -131,10 +145,7 @@ void free_float_state(FloatState *s);
 }  // namespace fpldpc
 
 // Decoder object (fpldpc_decoder_t): device-resident code description + kernel choice.
-struct fpldpc_decoder {
-    fpldpc_code code;
-    fpldpc_params params{};
-    int device = 0;
+struct fpldpc_decoder : fpldpc::DecoderCore {
     fpldpc::KernelChoice kc;
     fpldpc::DeviceCode dcode;
     uint16_t *d_vidx = nullptr;
@@ -149,15 +160,8 @@ struct fpldpc_decoder {
     bool stationary_exit = true;    // FPLDPC_STATIONARY_EXIT=0 at creation: every frame runs its iterations (A/B runs)
     std::string diag_trace_path;    // FPLDPC_WG_TRACE at creation
     int fb_cap = 0;
-    int32_t *d_info_idx = nullptr;
-    uint8_t *d_info_bits = nullptr;
-    uint32_t *d_info_mask = nullptr;  // packed [2][hard words] when the info positions are distinct
-    int k_info = 0;
-    // staging for fpldpc_decode_host
-    hipStream_t stream = nullptr;
+    uint32_t *d_info_mask = nullptr;  // the reference as plan::reference_mask when the info positions are distinct
     hipEvent_t last_done = nullptr;  // recorded after each (uncaptured) decode: fallback_counts waits on it
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
     fpldpc::FloatState *fl = nullptr;
     fpldpc::EdgeTables edges;        // fpldpc_decode_frame tables (first use)
     int32_t *d_edge_stage = nullptr; // fpldpc_decode_frame_host staging: llr, edge RAM, post, hard, iters, ok

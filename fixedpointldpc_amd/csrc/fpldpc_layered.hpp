@@ -5,11 +5,9 @@
 // fpldpc_minsum_device.hpp the min-sum rule).
 //
 // The layered decoder is an object of its own, not a mode of fpldpc_decoder: its state differs (the
-// c2v of every check persists across layers).  What every decoder object has, and the host plumbing around
-// it (creation checks, reference bits, the checks of a decode call, the staged host decode), is
-// fpldpc_host.hpp's DecoderCore, which this object is built on.  The flooding decoder's object
-// (fpldpc_internal.hpp) still carries its own copy of that state: the kernel build id hashes the units that
-// are compiled against its layout.
+// c2v of every check persists across layers).  What every decoder object has is DecoderCore
+// (fpldpc_internal.hpp), which this object is built on as fpldpc_decoder is; the host plumbing around it
+// (creation checks, reference bits, the checks of a decode call, the staged host decode) is fpldpc_host.hpp's.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -324,7 +324,7 @@ int DecodeTrial(double EbN0_dB, int MaxPacket) {
                 fpldpc_compat::check(fpldpc_decode(decs[r], d_llr, FPLDPC_LLR_I32, std::min(B, share[r] - done), nullptr,
                                                    (int32_t *)d_it, nullptr, nullptr, nullptr, nullptr, nullptr),
                                      "DecodeTrial");
-            if (hipDeviceSynchronize() != hipSuccess) throw fpldpc_error(FPLDPC_ERR_HIP, "DecodeTrial: synchronize");
+            if (hipStreamSynchronize(nullptr) != hipSuccess) throw fpldpc_error(FPLDPC_ERR_HIP, "DecodeTrial: synchronize");
             const int last = share[r] > 0 ? share[r] - (share[r] - 1) / B * B : 0;
             its[r].resize((size_t)last);
             if (last > 0 && hipMemcpy(its[r].data(), d_it, (size_t)last * 4, hipMemcpyDeviceToHost) != hipSuccess)

@@ -63,11 +63,12 @@ namespace {
 struct Dec {
     fpldpc_decoder_t flood = nullptr;
     fpldpc_layered_t lay = nullptr;
-    explicit operator bool() const { return flood || lay; }
-    bool operator==(const Dec &o) const { return flood == o.flood && lay == o.lay; }
-    hipStream_t stream() const { return flood ? flood->stream : lay->stream; }
-    int device() const { return flood ? flood->device : lay->device; }
-    fpldpc_code &code() const { return flood ? flood->code : lay->code; }
+    DecoderCore *core() const { return flood ? static_cast<DecoderCore *>(flood) : lay; }
+    explicit operator bool() const { return core() != nullptr; }
+    bool operator==(const Dec &o) const { return core() == o.core(); }
+    hipStream_t stream() const { return core()->stream; }
+    int device() const { return core()->device; }
+    fpldpc_code &code() const { return core()->code; }
     int decode(const int16_t *llr, int32_t frames, uint32_t *hard, int32_t *iters, int32_t *bit_errors,
                hipStream_t st) const {
         return flood ? fpldpc_decode(flood, llr, FPLDPC_LLR_I16, frames, hard, iters, nullptr, nullptr, bit_errors, nullptr, st)

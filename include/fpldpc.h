@@ -168,7 +168,8 @@ int fpldpc_decode_frame_host(fpldpc_decoder_t dec, const int32_t *llr, int32_t k
 int fpldpc_decode_float(fpldpc_decoder_t dec, const double *llr, int32_t batch, uint32_t *hard,
                         int32_t *iters, uint8_t *syndrome_ok, double *post, int32_t *bit_errors,
                         int64_t *totals, void *stream);
-/* Same on host buffers (synchronous). */
+/* Same on host buffers (synchronous; stages through the decoder's device memory and stream, the ones
+ * fpldpc_decode_host uses). */
 int fpldpc_decode_float_host(fpldpc_decoder_t dec, const double *llr, int32_t batch, uint32_t *hard,
                              int32_t *iters, uint8_t *syndrome_ok, double *post, int32_t *bit_errors,
                              int64_t *totals);

@@ -1,5 +1,5 @@
-// host_plan_test.cpp -- CPU check of the decoders' host staging layout and slot-major index table
-// (fixedpointldpc_amd/csrc/fpldpc_host_plan.hpp) against their definitions restated here.
+// host_plan_test.cpp -- CPU check of the decoders' host staging layout, slot-major index table and packed
+// reference mask (fixedpointldpc_amd/csrc/fpldpc_host_plan.hpp) against their definitions restated here.
 //
 // Staging layout: for random (batch, n, element sizes, wanted outputs) the LLRs and every wanted output have a
 // 256-byte aligned region of at least their raw size inside the block, no two regions overlap, and an output
@@ -8,6 +8,8 @@
 // iters, syndrome flags, post, bit errors, totals).
 // Table: against a double loop over (check, slot) for random irregular codes, at pitch m and at m rounded up to
 // 64, in the code's own order and in a stable sort by degree, for two fill values.
+// Mask: random distinct position sets on n = 31, 32, 33, 169 and 2209 (positions 0, 31, 32 and n - 1 always
+// among them, bits any byte) against a loop over the variables; one position repeated gives the empty result.
 // Exit 0 = all trials agree.
 #include <algorithm>
 #include <cstdio>
@@ -111,6 +113,47 @@ int check_table(std::mt19937_64 &rng) {
     return bad;
 }
 
+// A set of k distinct positions of n (every one with full: k = n) holding 0, 31, 32 and n - 1 where they exist,
+// in random order, with bytes as bits: the mask against a loop over the variables; then the same list with each
+// of its positions in turn repeated at a random place, which must give the empty result.
+int check_mask(std::mt19937_64 &rng, int n, bool full) {
+    std::vector<int32_t> pos(n);
+    for (int v = 0; v < n; ++v) pos[v] = v;
+    std::shuffle(pos.begin(), pos.end(), rng);
+    const int32_t edge[4] = {0, 31, 32, n - 1};
+    int front = 0;
+    for (int32_t e : edge)
+        if (e < n && std::find(pos.begin(), pos.begin() + front, e) == pos.begin() + front)
+            std::iter_swap(std::find(pos.begin(), pos.end(), e), pos.begin() + front++);
+    const int k = full ? n : front + (int)(rng() % (n - front + 1));
+    pos.resize(k);
+    std::shuffle(pos.begin(), pos.end(), rng);
+    std::vector<uint8_t> bits(k);
+    for (auto &b : bits) b = (uint8_t)rng();  // any byte: only bit 0 counts
+    const size_t hw = ((size_t)n + 31) / 32;
+    std::vector<int> is_info(hw * 32, 0), ref(hw * 32, 0);
+    for (int i = 0; i < k; ++i) {
+        is_info[pos[i]] = 1;
+        ref[pos[i]] = bits[i] & 1;
+    }
+    const std::vector<uint32_t> mk = reference_mask(n, pos.data(), bits.data(), k);
+    int bad = mk.size() != 2 * hw;
+    for (size_t v = 0; !bad && v < hw * 32; ++v) {
+        bad += (int)(mk[v / 32] >> (v % 32) & 1) != is_info[v];
+        bad += (int)(mk[hw + v / 32] >> (v % 32) & 1) != ref[v];
+    }
+    for (int i = 0; i < k; ++i) {
+        std::vector<int32_t> p2 = pos;
+        std::vector<uint8_t> b2 = bits;
+        const size_t at = rng() % (k + 1);
+        p2.insert(p2.begin() + at, pos[i]);
+        b2.insert(b2.begin() + at, (uint8_t)rng());
+        bad += !reference_mask(n, p2.data(), b2.data(), k + 1).empty();
+    }
+    if (bad) fprintf(stderr, "mask: n %d k %d\n", n, k);
+    return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -118,6 +161,8 @@ int main() {
     int bad = 0, trials = 0;
     for (int t = 0; t < 20000; ++t, ++trials) bad += check_layout(rng) != 0;
     for (int t = 0; t < 300; ++t, ++trials) bad += check_table(rng) != 0;
+    for (int n : {31, 32, 33, 169, 2209})
+        for (int t = 0; t < 8; ++t, ++trials) bad += check_mask(rng, n, t == 0) != 0;
     printf("%d trials, %d mismatches\n", trials, bad);
     return bad != 0;
 }

@@ -69,6 +69,13 @@ def test_per_kernel_translation_units():
     assert "fpldpc::array47_pair_kernel()" in out and "fpldpc::table8_pair_kernel()" in out
 
 
+def test_host_entry_points_are_built_outside_the_build_id():
+    """Staging, describe and the shared plumbing reach a kernel only through the hashed launch units."""
+    from fixedpointldpc_amd import _build
+    for unit in ("fpldpc_decoder_api.cpp", "fpldpc_host.cpp"):
+        assert unit in _build.SOURCES and unit not in _build.HASHED_TUS, unit
+
+
 def test_version_and_defaults(F):
     lib = F.lib()
     assert b"gfx950" in lib.fpldpc_version()

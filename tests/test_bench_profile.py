@@ -64,7 +64,9 @@ def test_committed_profile_is_of_the_shipped_build(F):
     ids named instead of failing the suite; one summary must still hold one build's counters."""
     import glob
     import pytest
-    newest = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_traffic.json")))[-1]
+    import re
+    summaries = glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_traffic.json"))
+    newest = max(summaries, key=lambda p: int(re.fullmatch(r"r(\d+)", os.path.basename(os.path.dirname(p))).group(1)))
     ids = {e.get("kernel_build_id") for e in json.load(open(newest)).values()}
     assert len(ids) == 1, (newest, ids)
     built = F.lib().fpldpc_kernel_build_id().decode()

@@ -103,3 +103,42 @@ def test_every_output_subset(F, setup, kind):
                     calls += 1
                     assert np.array_equal(after[mask], TOT0 + calls * delta), f"{where}: totals after subset {mask:06b}"
             assert calls == 32
+
+
+# (entry point, LLR dtype, frames): the fixed-point and the float host decode of one flooding decoder in turn
+SHARED_CALLS = (("fpldpc_decode_host", np.int16, 3), ("fpldpc_decode_float_host", np.float64, 300),
+                ("fpldpc_decode_host", np.int32, 300), ("fpldpc_decode_float_host", np.float64, 2),
+                ("fpldpc_decode_host", np.int16, 2))
+
+
+def test_fixed_and_float_share_one_block(F, setup):
+    """The two host decodes of one flooding decoder object share its staging block and stream: the block is grown
+    by one family and reused by the other, with other element sizes and so other region offsets.  One decoder
+    (3 iterations, pre-check on, so the fixed-point calls' seeded posteriors of the noiseless frame must survive
+    what the float call left in the block) takes SHARED_CALLS in order, all six outputs each; every call's outputs
+    equal those of the same call on a fresh decoder of its own."""
+    code, llr16, info_index = setup
+
+    def make():
+        dec = F.Decoder(code, max_iter=3, precheck=True)
+        dec.set_reference(info_index, np.zeros(len(info_index), np.uint8))
+        return dec
+
+    def call(dec, entry, dt, B):
+        seed = (np.arange(B * N).reshape(B, N) % 251 - 125).astype(np.float64 if dt == np.float64 else np.int32)
+        bufs = [np.full((B, HW), 0xA5A5A5A5, np.uint32), np.full(B, -7, np.int32), np.full(B, 9, np.uint8), seed.copy(),
+                np.full(B, -3, np.int32), TOT0.copy()]
+        assert _call(F, dec, entry, _llr(llr16, B, dt), bufs) == 0, F.lib().fpldpc_last_error().decode()
+        return dict(zip(OUTS, bufs)), seed
+
+    shared = make()
+    for i, (entry, dt, B) in enumerate(SHARED_CALLS):
+        where = f"call {i + 1}: {entry} {np.dtype(dt).name} batch {B}"
+        (got, seed), (want, _) = call(shared, entry, dt, B), call(make(), entry, dt, B)
+        # the fresh decoder's call did its work: every output written, its totals this batch's sums
+        assert (want["iters"] >= 0).all() and (want["iters"] <= 3).all() and (want["bit_errors"] >= 0).all(), where
+        assert want["syndrome_ok"][0] == 1 and (want["post"][1:] != seed[1:]).any(), where
+        assert np.array_equal(want["totals"] - TOT0, [want["bit_errors"].sum(), (want["bit_errors"] > 0).sum(), B,
+                                                      want["iters"].sum()]), where
+        for name in OUTS:
+            assert np.array_equal(got[name], want[name]), f"{where}: {name}"

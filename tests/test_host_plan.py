@@ -1,9 +1,10 @@
-"""The decoders' host staging layout and slot-major index table (fpldpc_host_plan.hpp, used by the staged host
-decode and the decoders' table upload) on the CPU, against their definitions restated in
-tests/cpp/host_plan_test.cpp: 20000 random layouts (alignment, disjoint regions in bounds, the fixed-point
-decoders' long-standing offsets when every output is wanted) and 300 random irregular codes (pitch m and m
-rounded up to 64, the code's own order and a stable sort by degree).  Built a second time with the address and
-undefined-behaviour sanitizers."""
+"""The decoders' host staging layout, slot-major index table and packed reference mask (fpldpc_host_plan.hpp, used
+by the staged host decode, the decoders' table upload and fpldpc_set_reference) on the CPU, against their
+definitions restated in tests/cpp/host_plan_test.cpp: 20000 random layouts (alignment, disjoint regions in bounds,
+the fixed-point decoders' long-standing offsets when every output is wanted), 300 random irregular codes (pitch m
+and m rounded up to 64, the code's own order and a stable sort by degree) and 40 position sets on n = 31, 32, 33,
+169 and 2209 (the mask bit by bit; empty with any one position repeated).  Built a second time with the address
+and undefined-behaviour sanitizers."""
 import os
 import shutil
 import subprocess
