@@ -136,6 +136,7 @@ SIGNATURES = {
     "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
     "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
     "fpldpc_testing_stationary_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
+    "fpldpc_testing_cycle_exits": (ctypes.c_int, [P, ctypes.POINTER(I32)]),
     "fpldpc_testing_float_describe": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
 }
 EXPORTED = list(SIGNATURES)
@@ -415,6 +416,12 @@ class Decoder(_DecoderBase):
         """Frames the last completed decode call ended by the stationary exit (include/fpldpc_testing.h)."""
         c = ctypes.c_int32(0)
         _check(lib().fpldpc_testing_stationary_exits(self._h, ctypes.byref(c)))
+        return c.value
+
+    def cycle_exits(self):
+        """Frames the last completed decode call ended by the cycle exit (include/fpldpc_testing.h)."""
+        c = ctypes.c_int32(0)
+        _check(lib().fpldpc_testing_cycle_exits(self._h, ctypes.byref(c)))
         return c.value
 
     def float_describe(self):

@@ -129,6 +129,7 @@ int create_decoder(const fpldpc_code *code, const fpldpc_params *params, const K
     // Diagnostics, read once here rather than on every decode call (see fpldpc_decode)
     if (const char *sp = getenv("FPLDPC_SPLIT_TAIL")) d->split_tail = *sp != '0';
     if (const char *se = getenv("FPLDPC_STATIONARY_EXIT")) d->stationary_exit = *se != '0';
+    if (const char *ce = getenv("FPLDPC_CYCLE_EXIT")) d->cycle_exit = *ce != '0';
     if (diag) {
         const char *probe_env = getenv("FPLDPC_CLOCK_PROBE");
         d->diag_probe = probe_env && *probe_env == '1';
@@ -219,6 +220,7 @@ int fpldpc_decode(fpldpc_decoder_t dec, const void *llr, int32_t llr_type, int32
     a.bfe_w = (uint32_t)std::max(0, __builtin_popcount((unsigned)a.mask) - 2);
     a.split_tail = dec->split_tail ? 1 : 0;
     a.stationary_exit = dec->stationary_exit ? 1 : 0;
+    a.cycle_exit = dec->cycle_exit ? 1 : 0;
     if (dec->kc.fallback != Variant::kNone) {
         if (batch > dec->fb_cap) {  // grows to the largest batch seen (not inside graph capture)
             (void)hipFree(dec->d_fb_list);

@@ -75,6 +75,19 @@ int fpldpc_testing_stationary_exits(void *decoder, int32_t *count) {
     return FPLDPC_OK;
 }
 
+// Test-only (include/fpldpc_testing.h): frames the last completed decode call ended by the cycle exit.
+int fpldpc_testing_cycle_exits(void *decoder, int32_t *count) {
+    fpldpc_decoder_t dec = static_cast<fpldpc_decoder_t>(decoder);
+    if (!dec || !count) return fail(FPLDPC_ERR_ARG, "null argument");
+    *count = 0;
+    if (dec->kc.fallback == Variant::kNone || dec->kc.fallback2 != Variant::kNone) return FPLDPC_OK;
+    int32_t c[kCounterInts];
+    const int st = last_counters(dec, c);
+    if (st) return st;
+    *count = c[kCountCycLast];
+    return FPLDPC_OK;
+}
+
 int fpldpc_edge_ram_words(fpldpc_decoder_t dec, int64_t *words) {
     if (!dec || !words) return fail(FPLDPC_ERR_ARG, "null argument");
     *words = (int64_t)dec->code.dc_max * dec->code.m;

@@ -444,10 +444,14 @@ struct ArrayChecks {
     static constexpr int kStatWords = P * NT;  // scratch words per workgroup
     static constexpr int kStatSlots = P;       // state words compared in the packed form
     static constexpr int kStatSplitSlots = (P - 1) / 2 + 1;  // in the split form (the pairs S[0..SL])
-    template <int SLOTS>
-    __device__ __forceinline__ uint32_t stat_verify(uint32_t *slice, int tid, bool compare) const {
+    // HOLD (the split tail's cycle exit, DESIGN.md "Cycle exit (round 21)"): with `keep` (wave-uniform) the
+    // rows are compared and left as they are -- a snapshot held over several steps -- through a branch
+    // round each batch's stores, in the same one instruction stream; the split form has the registers
+    // for eight loads in flight.  Without HOLD the code is what it was.
+    template <int SLOTS, bool HOLD = false>
+    __device__ __forceinline__ uint32_t stat_verify(uint32_t *slice, int tid, bool compare, bool keep = false) const {
         uint32_t chg = 0;
-        constexpr int G = 4;  // loads in flight per lane
+        constexpr int G = HOLD ? 8 : 4;  // loads in flight per lane
         asm volatile("" : "+v"(tid));
 #pragma unroll
         for (int k0 = 0; k0 < SLOTS; k0 += G) {
@@ -459,13 +463,30 @@ struct ArrayChecks {
                     if (k0 + g < SLOTS) old[g] = p[g * NT + tid];
             }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (HOLD) {
+                uint32_t nw[G] = {};
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int k = k0 + g;
-                if (k >= SLOTS) break;
-                const uint32_t x = st[0][k], nw = x + ((x & 0x8000u) << 1);
-                chg |= old[g] ^ nw;
-                p[g * NT + tid] = nw;
+                for (int g = 0; g < G; ++g) {
+                    const int k = k0 + g;
+                    if (k >= SLOTS) break;
+                    const uint32_t x = st[0][k];
+                    nw[g] = x + ((x & 0x8000u) << 1);
+                    chg |= old[g] ^ nw[g];
+                }
+                if (!keep) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+                        if (k0 + g < SLOTS) p[g * NT + tid] = nw[g];
+                }
+            } else {
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const int k = k0 + g;
+                    if (k >= SLOTS) break;
+                    const uint32_t x = st[0][k], nw = x + ((x & 0x8000u) << 1);
+                    chg |= old[g] ^ nw;
+                    p[g * NT + tid] = nw;
+                }
             }
             asm volatile("" : "+v"(chg));  // (this batch's words are dead from here on)
             __builtin_amdgcn_sched_barrier(0);

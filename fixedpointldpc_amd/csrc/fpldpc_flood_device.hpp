@@ -69,7 +69,8 @@ struct KArgs {
     unsigned long long *wgtrace;  // diagnostic (FPLDPC_WG_TRACE): per workgroup {xcc<<32 | hw_id, start, end, frames, stamps[4]}
     int *counters;       // the decoder's counter block (fpldpc_internal.hpp kCounterInts)
     int last_in_chain;   // 1: this launch is the call's last kernel and resets the counter block
-    int split_tail;      // packed array kernels: a lone frame continues in the split form (flood_pk)
+    int split_tail;      // packed array kernels: a lone frame continues in the split form (flood_pk); bit 1: the A
+                         // kernel's cycle exit in that form is on
 };
 
 __device__ __forceinline__ void clock_probe(const KArgs &a, int slot) {

@@ -66,10 +66,11 @@ struct StatCtl<true> {
     //   bits 2-3   the same halves' `changed` flags, wanted too -- set only while the exit is on
     //   bits 16-19 the verification state vs, two bits per half (1: the coming step stores, 2: it
     //              compares); no flag word has these bits, so the quick exit is not taken meanwhile
-    // A flag word (misc[6..8]) only ever carries bits 0-5: fail (0, 1), changed (2, 3), the compare's
-    // result (4, 5).  Bits 16-19 of q_live must stay outside that set (kFlagBits), and both loops read
-    // the state through on() / vs() only.
-    static constexpr int kFlagBits = 0x3f;
+    // A flag word (misc[6..8]) only ever carries bits 0-6: fail (0, 1), changed (2, 3), the compare's
+    // result (4, 5) and, in the split loop only, the cycle exit's arming bit (6: some live check lane's
+    // posterior hash did not change).  Bits 16-19 of q_live must stay outside that set (kFlagBits), and
+    // both loops read the state through on() / vs() only.
+    static constexpr int kFlagBits = 0x7f;
     static_assert((kFlagBits & 0xf0000) == 0, "the verification state must lie outside the flag bits");
     static __device__ __forceinline__ int word(int live, bool on, int vs) { return live * (on ? 5 : 1) | vs << 16; }
     static __device__ __forceinline__ bool on(int q_live) { return (q_live & 0xc) != 0; }
@@ -86,6 +87,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
     // misc: [0,1] frame of half h (-1 idle)  [2,3] start step  [4,5] load taint  [6..8] flag words
     //       [12] final-pass syndrome word  [13] deferred range-check word
     //       [9,10] bit-error accumulators  [14] frames this workgroup ended by the stationary exit
+    //       [15] frames it ended by the cycle exit
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u16x2 C2 = (u16x2)(unsigned short)a.C;
     uint32_t M2 = ((1u << a.bfe_w) - 1u) * 0x10001u;
@@ -130,6 +132,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
     // the queue empty and when the workgroup entered the split tail, and the steps it then ran with
     // two live frames, one live frame (packed) and in the split form (trace words 4..7)
     unsigned long long tt_empty = 0, tt_split = 0, tt_two = 0, tt_one = 0, tt_splits = 0;
+    int tt_frame = -1;  // the frame the workgroup carried into the split form (word 3, bits 32-63: id + 1)
 #endif
     // (Re)fill the halves in `mask` before step s: new frames' LLRs into llrc, into the buffer
     // read at step s (pc) and the one accumulated at step s (pn); c2v state and overflow trackers
@@ -431,9 +434,11 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             unsigned wg = blockIdx.x;  // (opaque: see stat_verify)
             asm volatile("" : "+s"(wg));
             uint32_t *const slice = reinterpret_cast<uint32_t *>(a.c2v_scratch) + (size_t)wg * CK::kStatWords;
-            const uint32_t chg = ck.template stat_verify<decltype(words_c)::value>(slice, tid, (sc.vs(q_live) & 0xa) != 0);
-            // (split form: both halves of a state word are the one frame's, in half 0 of the control words)
+            // (split form: both halves of a state word are the one frame's, in half 0 of the control words, and
+            // half 1's state bits are the cycle exit's part: 2 compares as well, and keeps the rows)
             constexpr bool kPacked = decltype(words_c)::value == CK::kStatSlots;
+            const uint32_t chg = ck.template stat_verify<decltype(words_c)::value, !kPacked>(slice, tid, (sc.vs(q_live) & 0xa) != 0,
+                                                                                             !kPacked && (sc.vs(q_live) & 8) != 0);
             const uint32_t lo = kPacked ? chg & 0xffffu : chg, hi = kPacked ? chg >> 16 : 0u;
             const uint32_t cb = (__ballot(lo != 0u) ? 0x10u : 0u) | (__ballot(hi != 0u) ? 0x20u : 0u);
             if (cb) atomicOr(&misc[6 + s % 3], (int)cb);
@@ -669,6 +674,60 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
         wt_bar2 += __builtin_amdgcn_s_memtime() - wd0;
 #endif
     }
+    // The cycle exit (split loop only, DESIGN.md "Cycle exit (round 21)").  The c2v messages are the whole
+    // state of the iteration (posterior = LLR + sum c2v, v2c = posterior - c2v), so a frame whose c2v after
+    // update u + P equal those after update u repeats from there with period P: update max_iter gives what
+    // update u + P + rem gives, rem = (max_iter - u - P) mod P.  The frame's start step is moved back by the
+    // whole periods left, and it ends through the max_iter path as if it had run them.
+    //   arm      some live check lane's posterior hash did not change (flag bit 6), more than 8 updates
+    //            are left, and no stationary verification is pending
+    //   snapshot the step after stores the c2v words in the scratch slice (the rows the stationary
+    //            verification uses: its trigger drops a held snapshot, so the two are never pending together)
+    //   hold     the 8 steps after that compare with the snapshot and store nothing (flag bit 4, as the
+    //            stationary compare); then a new snapshot, if still armed
+    // Its state rides in q_live too, in the split loop's own reading of the word (the lone frame is in half
+    // 0, so half 1's bits are free there; a new scalar alive in this loop, or one more branch on its quick
+    // path, cost the packed loop 20 VGPRs and spills):
+    //   bit 2      the exits are on for the frame (sc.on)      bit 3      the cycle exit is on
+    //   bits 18-19 the coming step's part, where half 1's verification state would be (1: it stores the
+    //              snapshot, 2: it compares and keeps it), so sc.vs and stat_check's compare flag cover it
+    //   bits 20-23 the steps since the snapshot while it is held
+    // The cycle exit's decisions after the barrier of step s, after stat_decide's; d = the frame's completed
+    // updates in pc, and the state compared is that of update d + 1.
+    [[maybe_unused]] auto cyc_decide = [&](uint32_t flags, int s) {
+        if constexpr (CK::kStationary) {
+            if (!(q_live & 8) || frm(0) < 0) return;
+            const int part = q_live >> 18 & 3, age = q_live >> 20 & 15, d = s - sst(0);
+            int nc = 0;
+            if (part == 1) {
+                nc = 2 << 18;  // this step stored the snapshot
+            } else if (part == 2) {
+                const int period = age + 1;
+                if (!(flags & 0x10u)) {
+                    if (period == 1) {
+                        // the stationary proof itself: update d + 1 reproduced the c2v of update d
+                        sc.stat |= 1;
+                    } else if ((flags & 1u) || !a.early_term) {  // (a satisfied syndrome ends the frame by itself)
+                        int rem = a.max_iter - (d + 1);
+                        const int left = rem;
+                        while (rem >= period) rem -= period;
+                        if (left > rem) {
+                            sst_r[0] -= left - rem;
+                            q_until = sst_r[0] + a.max_iter - 1;
+                            q_live &= 0xfff3;  // the exits are off for the rest of this frame
+                            if (tid == 0) misc[15] += 1;
+                            return;
+                        }
+                    }
+                } else if (period < 8) {
+                    nc = 2 << 18 | period << 20;
+                }
+            }
+            if (nc == 0 && (flags & 0x40u) && a.max_iter - d > 8) nc = 1 << 18;
+            if ((sc.vs(q_live) & 3) || (sc.stat & 1)) nc = 0;  // the stationary exit keeps precedence (and the rows)
+            q_live = (q_live & 0x3ffff) | nc;
+        }
+    };
     // (the split loop's step)
     auto step_body = [&](int s, auto split_c) -> bool {
         constexpr bool SPLIT = decltype(split_c)::value;
@@ -688,6 +747,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 t[7] = FPLDPC_PHASE_TRACE == 3 ? ph_rload : ph_steps;
 #endif
 #if FPLDPC_TAIL_TRACE
+                t[3] |= (unsigned long long)(unsigned)(tt_frame + 1) << 32;
                 t[4] = tt_empty;
                 t[5] = tt_split;
                 t[6] = tt_two | tt_one << 32;
@@ -749,6 +809,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             ck.step(a, pc, pn, lds_addr(pc), lds_addr(pn), C2, M2, par, ovor);
         ovf |= ovor;
         if constexpr (CK::kStationary) {  // (nested: the outer condition does not depend on the lambda's parameter)
+            // (the stationary verification, or the cycle exit's snapshot / compare)
             if constexpr (SPLIT) stat_check(std::integral_constant<int, CK::kStatSplitSlots>{}, s);
         }
         // per-step flags: fail (syndrome) for each half, OR over the block.  The int16 range flags
@@ -760,8 +821,15 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             uint32_t wb = 0;
 #pragma unroll
             for (int b = 0; b < 2; ++b) wb |= __ballot((bits >> b) & 1u) ? (1u << b) : 0u;
-            if constexpr (CK::kStationary)  // (the trigger, as in the packed loop; the frame is in half 0)
+            if constexpr (CK::kStationary) {  // (the trigger, as in the packed loop; the frame is in half 0)
                 wb |= __ballot((par & 0x7fffu) != 0u) ? 4u : 0u;
+                // the cycle exit's arming bit, while it is on: the hashes of kCycArm live check lanes of one wave
+                // did not change.  (One lane is not enough: the posteriors are small numbers, and the 15-bit XOR
+                // of a check's 47 stays the same by chance in about one check in a hundred per update, at 2 dB
+                // in some check at nearly every step; a cycling frame leaves 11 and more lanes of a wave unchanged.)
+                constexpr int kCycArm = 8;
+                wb |= __popcll(__ballot(tid < a.m && (par & 0x7fffu) == 0u)) >= kCycArm ? (uint32_t)(q_live & 8) << 3 : 0u;
+            }
             if (lane == 0 && wb) atomicOr(&misc[6 + s % 3], (int)wb);
         }
         __syncthreads();
@@ -773,7 +841,7 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
                 if (frm(h) >= 0) q = q && (flags >> h & 1u) && s < sst(h) + a.max_iter - 1;
             // (the stationary exit: the frame's posteriors changed, and no verification is pending)
             if constexpr (CK::kStationary)
-                if (sc.on(q_live)) q = q && (flags >> 2 & 1u) && !sc.vs(q_live);
+                if (sc.on(q_live)) q = q && (flags & 0x44u) == 4u && !sc.vs(q_live);
             if (q) {
                 cur = (cur + 1) % 3;
                 return true;
@@ -782,6 +850,8 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
         // (the stationary exit as in the packed loop; the frame is in half 0, and of the posterior words
         // only that half is the frame's: half 1's `changed` and compare bits are never looked at)
         if constexpr (CK::kStationary) stat_decide(flags, s);
+        // (the cycle exit, before the end decisions: a frame it leaves no update to ends in this step)
+        if constexpr (CK::kStationary) cyc_decide(flags, s);
         // When no frame ends on pc's syndrome but every frame still running has just made its last
         // update (max_iter) into pn, check pn now (one syndrome pass after the barrier) instead of in
         // the next step's gather: a frame then costs max_iter check updates, not max_iter + 1.
@@ -904,9 +974,11 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
             ck.split_enter(h);
             // (the scratch words are the packed state's: a pending verification starts over from the
             // trigger, which a stationary frame sets again at every step)
-            if constexpr (CK::kStationary) q_live &= 0xffff;
+            // (and the word in the split loop's reading: bit 2 the exits on, bit 3 the cycle exit on)
+            if constexpr (CK::kStationary) q_live = sc.on(q_live) ? ((a.split_tail & 2) ? 12 : 4) : 0;
 #if FPLDPC_TAIL_TRACE
             if (tid == 0) tt_split = __builtin_amdgcn_s_memrealtime();
+            tt_frame = frm_r[0];
 #endif
             __syncthreads();
             for (;; ++s)
@@ -920,6 +992,17 @@ __global__ void __launch_bounds__(NT, WAVES) flood_pk(KArgs a) {
         if (a.c2v_scratch && tid == 0 && misc[14]) {
             const int was = atomicAdd(&a.counters[kCountFb1], misc[14]);
             asm volatile("" ::"v"(was));
+        }
+        // the call's cycle exits, in a counter word of their own that this kernel keeps by itself (the
+        // chain's last kernel knows nothing of it): every workgroup counts itself out in the word's low
+        // kCycOutBits bits and adds its exits above them; the last one out leaves the sum for the host
+        // and zeroes the word for the next call (plain stores, seen at the kernel boundary as chain_reset's).
+        if (a.c2v_scratch && (a.split_tail & 2) && tid == 0) {
+            const int was = atomicAdd(&a.counters[kCountCyc], (misc[15] << kCycOutBits) | 1);
+            if ((was & ((1 << kCycOutBits) - 1)) == (int)gridDim.x - 1) {
+                a.counters[kCountCycLast] = (was >> kCycOutBits) + misc[15];
+                a.counters[kCountCyc] = 0;
+            }
         }
     }
     if (a.totals && tid == 0) {  // this workgroup's frames (each counter < 2^31 per workgroup)

@@ -77,6 +77,7 @@ struct LaunchArgs {
     unsigned long long *wgtrace = nullptr;  // diagnostic per-workgroup trace [grid][4] (host-mapped), or null
     int split_tail = 1;            // packed array kernels: a lone frame continues in the split form
     int stationary_exit = 1;       // the A kernel ends frames whose messages have stopped changing (flood_pk)
+    int cycle_exit = 1;            // and, in the split tail, frames whose messages cycle with a period up to 8
 };
 
 enum class Variant { kNone, kArray47x2, kArray47x2og, kArray47x2c2, kArray47x2c2t, kArray47x2mix, kArray47, kLds16_47, kTab8x4lo3, kTab8x4p, kReg47x1Regular, kReg8x4, kReg8x1, kReg16x2, kGmem8, kGmem16, kGmem32, kGmem48, kGmem64 };
@@ -104,9 +105,14 @@ struct KernelChoice {
 // [5] workgroups out of the call's last kernel, [6] / [7] the last call's list 0 / 1 sizes.
 // A chain of two kernels has no list 1: there the A kernel counts its stationary exits in [4], and [7]
 // holds the last call's (fpldpc_testing_stationary_exits; fpldpc_decoder_fallback_counts reports 0).
+// [8] the A kernel's cycle exits of the running call above its workgroups counted out (kCycOutBits), kept
+// and zeroed by that kernel alone; [9] the last call's cycle exits (fpldpc_testing_cycle_exits).
 // Zeroed once at decoder creation; the last workgroup of each call's last kernel resets [0..5]
 // (chain_exit, fpldpc_flood_device.hpp), so a decode call issues kernels only.
-constexpr int kCounterInts = 8;
+constexpr int kCounterInts = 10;
+constexpr int kCountCyc = 8;
+constexpr int kCountCycLast = 9;
+constexpr int kCycOutBits = 12;  // grids of up to 4095 workgroups (launch_decode leaves the exit off above that)
 constexpr int kCountFb0 = 2;
 constexpr int kCountFb1 = 4;
 constexpr int kCountExit = 5;
@@ -158,6 +164,7 @@ struct fpldpc_decoder : fpldpc::DecoderCore {
     bool diag_probe = false;        // FPLDPC_CLOCK_PROBE=1 at creation
     bool split_tail = true;         // FPLDPC_SPLIT_TAIL=0 at creation: no split form in the tail (A/B runs)
     bool stationary_exit = true;    // FPLDPC_STATIONARY_EXIT=0 at creation: every frame runs its iterations (A/B runs)
+    bool cycle_exit = true;         // FPLDPC_CYCLE_EXIT=0 at creation: cycling frames run theirs (the stationary exit stays)
     std::string diag_trace_path;    // FPLDPC_WG_TRACE at creation
     int fb_cap = 0;
     uint32_t *d_info_mask = nullptr;  // the reference as plan::reference_mask when the info positions are distinct

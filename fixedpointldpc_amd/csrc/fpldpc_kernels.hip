@@ -344,6 +344,9 @@ int launch_decode(const KernelChoice &kc, const DeviceCode &dcode, const LaunchA
     if (vi->stat_words && !(la.stationary_exit && kc.fallback2 == Variant::kNone)) a.c2v_scratch = nullptr;
     const int per_wg = vi->lds_state ? 1 : 2;  // frames in flight per workgroup
     const int grid = std::min(kc.grid, (la.batch + per_wg - 1) / per_wg);
+    // The cycle exit of the split tail shares that scratch, and its counter word counts the grid's workgroups
+    // out in kCycOutBits bits.
+    if (vi->stat_words && a.c2v_scratch && a.split_tail && la.cycle_exit && grid < (1 << kCycOutBits)) a.split_tail |= 2;
     hipLaunchKernelGGL(vi->fn, dim3(grid), dim3(kc.threads), kc.lds_bytes, s, a);
     e = hipGetLastError();
     if (e != hipSuccess) return launch_failed(e, "kernel launch");

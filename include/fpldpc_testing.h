@@ -35,6 +35,14 @@ uint32_t fpldpc_testing_range_guard(int32_t dv_max, int32_t C, int32_t slots, in
  * the environment at its creation.  Returns an fpldpc status. */
 int fpldpc_testing_stationary_exits(void *decoder, int32_t *count);
 
+/* The number of frames that the last completed fpldpc_decode call of `decoder` ended by the same kernel's
+ * cycle exit: frames whose check-to-variable messages, while the frame ran alone in the tail's split
+ * form, equalled those of 2 to 8 updates earlier, reported with max_iter iterations and the outputs
+ * max_iter updates give.  0 for a decoder whose kernel has no such exit, or with FPLDPC_CYCLE_EXIT=0,
+ * FPLDPC_STATIONARY_EXIT=0 or FPLDPC_SPLIT_TAIL=0 in the environment at its creation.  Returns an fpldpc
+ * status. */
+int fpldpc_testing_cycle_exits(void *decoder, int32_t *count);
+
 /* Which kernel fpldpc_decode_float launches for `decoder` (an fpldpc_decoder_t), its persistent grid and
  * the planes of its edge scratch, written to buf (at most len bytes) as one of
  *   bp_float_reg<DC=47,regular,array> grid=N planes=1    regular degree 47, variable indices computed

@@ -2,7 +2,8 @@
 """The early-termination tail of one packed-kernel launch, from an FPLDPC_WG_TRACE file of the
 FPLDPC_TAIL_TRACE=1 diagnostic build (flood_pk: trace words 4..7 = thread 0's s_memrealtime when a
 pull first found the queue empty, when the workgroup entered the split tail, the steps it then ran
-with two live frames | one live frame (packed) << 32, and the steps in the split form).
+with two live frames | one live frame (packed) << 32, and the steps in the split form; word 3 carries
+the frame the workgroup took into the split form, id + 1, above the frames pulled).
 
 Prints (and with --json writes) when the queue emptied, how the launch's workgroup-time after that
 splits into two live frames / one live frame / the split form, the histogram of how long each
@@ -71,6 +72,11 @@ def analyse(path):
         "cu_last_workgroup_alone_us": {"mean": float(np.mean(alone)), "p90": float(np.percentile(alone, 90)),
                                         "max": float(np.max(alone))},
         "end_us_percentiles": {q: float(np.percentile(end, q)) for q in (10, 50, 90, 99, 100)},
+        # the workgroups that ended last: the frame each carried into the split form (-1: none), the steps it
+        # ran there, and how long after the first empty pull anywhere it ended
+        "last_workgroups": [{"end_us": float(end[i]), "after_queue_empty_us": float(end[i] - q_empty),
+                             "split_frame": int(t[i, 3] >> np.uint64(32)) - 1, "split_steps": int(spl[i]),
+                             "split_us": float(t_split[i])} for i in np.argsort(end)[::-1][:16]],
         "live_curve": [[float(x), int(v)] for x, v in zip(grid[::20], live[::20])],
     }
     return out
