@@ -478,7 +478,7 @@ class LayeredDecoder(_DecoderBase):
     fpldpc_layered_create_sat, which is defined for every input.  check="minsum" (with both widths;
     scale_16 / 16 and offset correct the minimum) gives the min-sum decoder with compressed check state
     of fpldpc_layered_create_minsum; check="sxor", the default, is the reference's box-plus fold.
-    The min-sum decoder takes every loadable code (n <= 65535, check degrees 2..64): where its state does
+    The min-sum decoder takes every loadable code (n <= 65535, check degrees 2..255): where its state does
     not fit LDS it lives in global memory (describe: "mem=global ... scratch=<bytes>")."""
 
     _ENTRY = _entries("fpldpc_layered")
@@ -507,7 +507,7 @@ class LayeredDecoder(_DecoderBase):
 class MinSumDecoder(LayeredDecoder):
     """fpldpc_minsum_t: normalised / offset min-sum (scale_16 / 16 and offset correct the minimum) with the
     clamps and the compressed check state of the layered min-sum decoder, on the flooding schedule.
-    Defined for every input, and for every loadable code (n <= 65535, check degrees 2..64): where the check
+    Defined for every input, and for every loadable code (n <= 65535, check degrees 2..255): where the check
     state and the accumulators do not fit LDS they live in global memory (describe: "mem=global ...
     scratch=<bytes>").  Same outputs and methods as Decoder / LayeredDecoder."""
 

@@ -1,6 +1,6 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
 // (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* and fpldpc_minsum_* C ABI), fpldpc_layered.hip,
-// fpldpc_layered_minsum.hip, fpldpc_minsum.hip and fpldpc_minsum_global.hip (kernels; through
+// fpldpc_layered_minsum.hip, fpldpc_minsum.hip, fpldpc_minsum_global.hip and fpldpc_minsum_wide.hip (kernels; through
 // fpldpc_layered_device.hpp, beside which fpldpc_layered_host.hpp holds their shared choice and launch steps and
 // fpldpc_minsum_device.hpp the min-sum rule).
 //
@@ -30,7 +30,7 @@ enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3, kFloodMinsum
 // Kernel choice of a layered decoder, made once at creation.
 struct LayeredChoice {
     int mode = kLayUnsat;
-    int dc = 0;              // kernel DC: 8 / 16 / 32 / 48 / 64 >= dc_max, or the exact degree (47)
+    int dc = 0;              // kernel DC: 8 / 16 / 32 / 48 / 64 >= dc_max, or the exact degree (47); wide: 32 * sign words
     bool lds_state = false;  // c2v / check state (and the index table) in LDS; else per-workgroup global scratch
     bool computed = false;   // forward array code: v = k*p + (j + i*k) mod p, no index table
     bool table_lds = false;  // the index table is staged in LDS (with lds_state, table codes)
@@ -39,6 +39,8 @@ struct LayeredChoice {
     int grid = 0;            // resident workgroups (persistent)
     size_t lds_bytes = 0;
     size_t scratch_bytes = 0; // global c2v: grid * dc_max * m entries of the state type; min-sum: grid * slice
+    bool wide = false;        // min-sum: the wide form (fpldpc_minsum_wide.hip: run-time slot loops, degrees to 255)
+    int state_bytes = 16;     // min-sum: bytes of check state per check (wide: 8 + 4 * sign words)
     char name[96] = "";
 };
 
@@ -86,6 +88,14 @@ int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int sc
 bool minsum_state_forced_global(const char *env);
 int minsum_global_choose(const fpldpc_code &code, int device, LayeredChoice *lc);
 int minsum_global_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// The wide form of the two min-sum decoders (fpldpc_minsum_wide.hip; lc.wide), which the two pairs above
+// delegate to for a code with check degrees above 64 and for every code under FPLDPC_MINSUM_FORM=wide (a
+// diagnostic, read at creation).  minsum_wide_choose makes the whole choice for (mode, threads): check degrees
+// 2..255, the state in LDS where it fits unless force_global, the index table placed under `table_env`.
+bool minsum_form_forced_wide();
+int minsum_wide_choose(const fpldpc_code &code, int mode, int threads, const char *table_env, bool force_global, int device,
+                       LayeredChoice *out);
+int minsum_wide_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
 // A second layered object of src's code, parameters, L, layers, widths, scale, offset, device and LayeredChoice
 // (copied, not chosen again: the environment switches read at creation may have changed since), with device
 // tables, counter block, scratch and stream of its own: fpldpc_layered_ber_sim's and fpldpc_minsum_ber_sim's

@@ -126,12 +126,17 @@ MinsumFn minsum_fn(const LayeredChoice &lc) {
 
 }  // namespace
 
-// Envelope: check degrees 2..64, any valid layer size and n <= 65535.  The kernels of this unit where the
+// Envelope: check degrees 2..255, any valid layer size and n <= 65535.  A code with a check degree above 64,
+// and every code under FPLDPC_MINSUM_FORM=wide, takes the wide form (fpldpc_minsum_wide.hip).  Else the
+// kernels of this unit where the
 // int16 posteriors, the control words, 16 bytes per check and one byte per check of the degree table
 // (unless the kernel's DC is every check's degree) fit the CU's 160 KiB of LDS; there the index table is
 // placed as in layered_choose (FPLDPC_LAYERED_TABLE=global / lds places it regardless).  Every other code,
 // and every code under FPLDPC_LAYERED_MINSUM_STATE=global, takes the global form (fpldpc_minsum_global.hip).
 int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredChoice *out) {
+    if (code.dc_max > 64 || minsum_form_forced_wide())
+        return minsum_wide_choose(code, kLayMinsum, std::min(kLayMaxNT, (L + 63) / 64 * 64), "FPLDPC_LAYERED_TABLE",
+                                  minsum_state_forced_global("FPLDPC_LAYERED_MINSUM_STATE"), device, out);
     LayeredChoice lc;
     if (int st = lay_choice_of_code(code, kLayMinsum, "layered", &lc)) return st;
     lc.threads = std::min(kLayMaxNT, (L + 63) / 64 * 64);
@@ -146,6 +151,7 @@ int layered_minsum_choose(const fpldpc_code &code, int L, int device, LayeredCho
 }
 
 int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream) {
+    if (lc.wide) return minsum_wide_launch(lc, args, scale_16, offset, stream);
     if (!lc.lds_state) return minsum_global_launch(lc, args, scale_16, offset, stream);
     return lay_launch(minsum_fn(lc), lc, args, MinsumArgs{args, scale_16, offset}, stream, "layered min-sum");
 }

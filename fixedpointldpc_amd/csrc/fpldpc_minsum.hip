@@ -141,13 +141,17 @@ FloodMsFn flood_fn(const LayeredChoice &lc) {
 
 }  // namespace
 
-// Envelope: check degrees 2..64 and n <= 65535.  The kernels of this unit where the check state, three int32
+// Envelope: check degrees 2..255 and n <= 65535.  A code with a check degree above 64, and every code under
+// FPLDPC_MINSUM_FORM=wide, takes the wide form (fpldpc_minsum_wide.hip).  Else the kernels of this unit where the check state, three int32
 // accumulators, the int16 LLRs, the control words and one byte per check of the degree table (unless the
 // kernel's DC is every check's degree) fit the CU's 160 KiB of LDS; there the index table is placed as in
 // the layered decoders, under a switch of its own (FPLDPC_MINSUM_TABLE=global / lds places it regardless).
 // Every other code, and every code under FPLDPC_MINSUM_STATE=global, takes the global form
 // (fpldpc_minsum_global.hip).
 int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out) {
+    if (code.dc_max > 64 || minsum_form_forced_wide())
+        return minsum_wide_choose(code, kFloodMinsum, std::min(kLayMaxNT, (code.m + 63) / 64 * 64), "FPLDPC_MINSUM_TABLE",
+                                  minsum_state_forced_global("FPLDPC_MINSUM_STATE"), device, out);
     LayeredChoice lc;
     if (int st = lay_choice_of_code(code, kFloodMinsum, "flooding min-sum", &lc)) return st;
     lc.threads = std::min(kLayMaxNT, (code.m + 63) / 64 * 64);
@@ -162,6 +166,7 @@ int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out)
 }
 
 int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream) {
+    if (lc.wide) return minsum_wide_launch(lc, args, scale_16, offset, stream);
     if (!lc.lds_state) return minsum_global_launch(lc, args, scale_16, offset, stream);
     return lay_launch(flood_fn(lc), lc, args, MinsumArgs{args, scale_16, offset}, stream, "flooding min-sum");
 }

@@ -250,8 +250,14 @@ int fpldpc_layered_create_sat(fpldpc_code_t code, const fpldpc_params *params, i
  * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
  * use them.  On chip a check keeps 16 bytes whatever its degree -- f(m1), f(m2), k1 and a 64-bit sign
  * word, from which every c2v[c][k] is rebuilt -- so there is no per-edge state.
- * Envelope: check degrees 2..64, a valid layering and n <= 65535 (every code the loader accepts); no code is
- * refused for its size.  Placement of the check state: in LDS wherever the int16 posteriors, the control
+ * Envelope: check degrees 2..255 (the degree tables are bytes; a degree above 255 is FPLDPC_ERR_UNSUPPORTED,
+ * "check degree above 255"), a valid layering and n <= 65535; no code is refused for its size.  A code with a
+ * check degree above 64 -- and, under the diagnostic FPLDPC_MINSUM_FORM=wide read at creation, any code; any other
+ * value is ignored -- takes the wide form: W = ceil(dc_max / 32) sign words in place of the 64-bit word, 8 + 4 W
+ * bytes per check { f(m1) | f(m2) << 16, k1 | parity << 31, W words of sign bits }, of which an all-zero entry is
+ * every message 0; in LDS wherever 2 n + (9 + 4 W) m + 18 bytes at most fit, else in slices of
+ * roundup((8 + 4 W) m, 256) bytes; describe names it layered_minsum_wide<DC=32 W,..>.  For the other codes:
+ * placement of the check state: in LDS wherever the int16 posteriors, the control
  * words and 16 (17 with mixed degrees) bytes per check, 2 n + 17 m + 16 bytes at most, fit the CU's 160 KiB,
  * with no global scratch; otherwise "global": LDS keeps the posteriors, the control words and (where they
  * fit) the degrees, and each resident workgroup keeps its frame's state [m] x 16 bytes in a slice of
@@ -307,8 +313,13 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
  *     2 <= msg_bits < post_bits <= 16,   1 <= scale_16 <= 16,   0 <= offset <= S_m.
  * params.frac_bits and params.width_mask are validated as for the other decoders; the arithmetic does not
  * use them.  A check keeps 16 bytes whatever its degree, as in the layered min-sum decoder; there is no
- * per-edge state.  Envelope: check degrees 2..64 and n <= 65535 (every code the loader accepts); outside it
- * FPLDPC_ERR_UNSUPPORTED (with a message); no code is refused for its size.  Placement of the state: in LDS
+ * per-edge state.  Envelope: check degrees 2..255 (the degree tables are bytes) and n <= 65535; outside it
+ * FPLDPC_ERR_UNSUPPORTED (with a message: "check degree above 255"); no code is refused for its size.  A code
+ * with a check degree above 64 -- and, under the diagnostic FPLDPC_MINSUM_FORM=wide read at creation, any code;
+ * any other value is ignored -- takes the wide form with the check state of the layered min-sum decoder's wide
+ * form (8 + 4 W bytes per check, W = ceil(dc_max / 32)): in LDS wherever 14 n + (9 + 4 W) m + 18 bytes at most
+ * fit, else in slices of roundup((8 + 4 W) m + 12 n, 256) bytes; describe names it flood_minsum_wide<DC=32 W,..>.  For the
+ * other codes: placement of the state: in LDS
  * wherever 14 n + 17 m + 32 bytes (three int32 accumulators, the int16 LLRs, the state and the degrees; the
  * index table joins them only where it fits) fit the CU's 160 KiB, with no global scratch; otherwise
  * "global": LDS keeps the int16 LLRs, the control words and (where they fit) the degrees, and each resident
