@@ -43,6 +43,8 @@ SOURCES = [
     "fpldpc_sim_source.hip",
     # the harvest of a simulation's failing frames (scan and ordered compaction): outside the build id too
     "fpldpc_harvest.hip",
+    # mean-shift importance sampling (the bias object and the patch kernel behind the channel's): outside the build id too
+    "fpldpc_bias.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -44,6 +44,13 @@ class SimResult(ctypes.Structure):
                 ("iter_sum", ctypes.c_int64), ("frames_decoded", ctypes.c_int64), ("seconds", ctypes.c_double)]
 
 
+class BiasSums(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("frame_errors", ctypes.c_int64), ("bit_errors", ctypes.c_int64),
+                ("sum_w", ctypes.c_double), ("sum_w2", ctypes.c_double), ("sum_w_fe", ctypes.c_double),
+                ("sum_w2_fe", ctypes.c_double), ("sum_w_be", ctypes.c_double), ("min_logw", ctypes.c_double),
+                ("max_logw", ctypes.c_double)]
+
+
 FPLDPC_COUNT_BITS = 0
 FPLDPC_COUNT_ITERS = 1
 # void (*on_frame)(void *ctx, int64_t frame, int32_t iterations, int64_t blkerror)
@@ -132,6 +139,19 @@ SIGNATURES = {
     "fpldpc_harvest_counts": (ctypes.c_int, [P, P]),
     "fpldpc_harvest_records": (ctypes.c_int, [P, I64, I64, P, P, P, P, P, P, P]),
     "fpldpc_harvest_classes": (ctypes.c_int, [P, P, P, P, I32, ctypes.POINTER(I32)]),
+    "fpldpc_bias_create": (ctypes.c_int, [I32, P, P, I32, ctypes.POINTER(P)]),
+    "fpldpc_bias_free": (None, [P]),
+    "fpldpc_bias_dims": (ctypes.c_int, [P, P]),
+    "fpldpc_bias_channel_llr_host": (ctypes.c_int, [P, I64, I64, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P, I32,
+                                                    P, I32]),
+    "fpldpc_bias_channel_llr": (ctypes.c_int, [P, I64, I64, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P, I32, P,
+                                               P, P]),
+    "fpldpc_ber_sim_biased": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, P, ctypes.POINTER(SimResult), P]),
+    "fpldpc_layered_ber_sim_biased": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, P,
+                                                     ctypes.POINTER(SimResult), P]),
+    "fpldpc_minsum_ber_sim_biased": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, P,
+                                                    ctypes.POINTER(SimResult), P]),
+    "fpldpc_bias_sums_get": (ctypes.c_int, [P, ctypes.POINTER(BiasSums)]),
     "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
     "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
     "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
@@ -268,7 +288,8 @@ class Code:
 
 def _entries(family, **irregular):
     """A decoder class's entry points: <family>_<method>, except where the ABI names them otherwise."""
-    names = ("destroy", "describe", "set_reference", "decode", "decode_host", "ber_sim", "ber_sim_multi", "ber_sim_harvest")
+    names = ("destroy", "describe", "set_reference", "decode", "decode_host", "ber_sim", "ber_sim_multi", "ber_sim_harvest",
+             "ber_sim_biased")
     return {**{k: f"{family}_{k}" for k in names}, **irregular}
 
 
@@ -375,11 +396,15 @@ class _DecoderBase:
             out["totals"] = tot
         return out
 
-    def ber_sim(self, snr, sigma, harvest=None, **kw):
+    def ber_sim(self, snr, sigma, harvest=None, bias=None, **kw):
         """Ordered BER/FER simulation around this decoder (fpldpc_ber_sim, fpldpc_layered_ber_sim,
         fpldpc_minsum_ber_sim): the reference harness's frame loop, batched.
         Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
-        patterns (<family>_ber_sim_harvest), the filled Harvest under the result's "harvest" key."""
+        patterns (<family>_ber_sim_harvest), the filled Harvest under the result's "harvest" key.
+        bias = a Bias: the simulation on the shifted channel (<family>_ber_sim_biased, with or without a
+        harvest), the Bias with its weighted sums under the result's "bias" key."""
+        if bias is not None:
+            return _biased_sim([self], snr, sigma, FPLDPC_COLL_HOST, bias, harvest, kw)[0]
         if harvest is not None:
             return _harvest_sim([self], snr, sigma, FPLDPC_COLL_HOST, harvest, kw)[0]
         p, keep = sim_params(snr, sigma, **kw)
@@ -798,14 +823,126 @@ def _harvest_sim(decoders, snr, sigma, collective, harvest, kw):
     return out, used.value
 
 
-def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, **kw):
+class Bias:
+    """fpldpc_bias_t: a mean shift on chosen positions for importance sampling (include/fpldpc.h).  positions are
+    strictly ascending in 0 .. n - 1; shifts is a scalar or one value per position, in units of the transmitted
+    amplitude (1 moves the mean to zero).  ber_sim(bias=...) runs on the shifted channel and leaves its weighted
+    sums in `sums`; channel_llr_biased / channel_llr_biased_torch are the channel on its own."""
+
+    def __init__(self, n, positions, shifts):
+        pos = np.ascontiguousarray(positions, np.int32).reshape(-1)
+        sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shifts, np.float64), pos.shape))
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_bias_create(n, _ptr(pos), _ptr(sh), len(pos), ctypes.byref(h)))
+        self._h = h
+        dims = np.zeros(2, np.int32)
+        _check(lib().fpldpc_bias_dims(self._h, _ptr(dims)))
+        self.n, self.count = int(dims[0]), int(dims[1])
+        self.positions, self.shifts = pos.copy(), sh.copy()
+
+    @classmethod
+    def from_harvest(cls, harvest, i, shift):
+        """The bias on the wrong bits of the harvest's record i."""
+        return cls(harvest.n, harvest.error_positions(i), shift)
+
+    @property
+    def sums(self):
+        """fpldpc_bias_sums of the last simulation run with this bias, as a dict."""
+        s = BiasSums()
+        _check(lib().fpldpc_bias_sums_get(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in BiasSums._fields_}
+
+    def estimate(self, k=None):
+        """fer = sum_w_fe / frames with its standard error, the effective sample size sum_w^2 / sum_w2, and with k
+        (information bits per frame) ber = sum_w_be / (frames * k)."""
+        s = self.sums
+        f = s["frames"]
+        fer = s["sum_w_fe"] / f
+        out = {"fer": fer, "fer_se": (max(s["sum_w2_fe"] / f - fer * fer, 0.0) / f) ** 0.5,
+               "ess": s["sum_w"] ** 2 / s["sum_w2"]}
+        if k is not None:
+            out["ber"] = s["sum_w_be"] / (f * k)
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.fpldpc_bias_free(self._h)
+            self._h = None
+
+
+_LLR_TYPES = {np.dtype(np.int16): FPLDPC_LLR_I16, np.dtype(np.int32): FPLDPC_LLR_I32, np.dtype(np.float64): FPLDPC_LLR_F64}
+
+
+def channel_llr_biased(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0):
+    """The shifted channel on the host (fpldpc_bias_channel_llr_host) for frames [first_frame, first_frame + frames);
+    cw: None, uint8 [n] (shared) or [frames][n] (per frame).  Returns (llr [frames][n], logw [frames])."""
+    out = np.empty((frames, bias.n), dtype)
+    logw = np.empty(frames, np.float64)
+    cwa = None if cw is None else np.ascontiguousarray(cw, np.uint8)
+    per = 1 if cwa is not None and cwa.ndim == 2 else 0
+    assert cwa is None or (cwa.shape[-1] == bias.n and (not per or cwa.shape[0] == frames))
+    _check(lib().fpldpc_bias_channel_llr_host(bias._h, seed, first_frame, frames, snr, sigma, frac_bits, _ptr(cwa), per,
+                                              _ptr(out), _LLR_TYPES[np.dtype(dtype)], _ptr(logw), nthreads))
+    return out, logw
+
+
+def channel_llr_biased_torch(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=None, device=None):
+    """The shifted channel on the device (fpldpc_bias_channel_llr) into new torch tensors on torch's current stream;
+    arguments as channel_llr_torch.  Returns (llr [frames, n], logw float64 [frames], overflow int32 [1])."""
+    import torch
+    dtype = dtype or torch.int16
+    device = torch.device(device if device is not None else (cw.device if cw is not None else "cuda"))
+    out = torch.empty((frames, bias.n), dtype=dtype, device=device)
+    logw = torch.empty(frames, dtype=torch.float64, device=device)
+    ovf = torch.zeros(1, dtype=torch.int32, device=device)
+    per = 0
+    if cw is not None:
+        assert cw.dtype == torch.uint8 and cw.is_cuda
+        cw = cw.contiguous()
+        per = 1 if cw.dim() == 2 else 0
+        assert cw.shape[-1] == bias.n and (not per or cw.shape[0] == frames)
+    t = {torch.int16: FPLDPC_LLR_I16, torch.int32: FPLDPC_LLR_I32, torch.float64: FPLDPC_LLR_F64}[dtype]
+    c = ctypes.c_void_p
+    with torch.cuda.device(device):
+        _check(lib().fpldpc_bias_channel_llr(bias._h, seed, first_frame, frames, snr, sigma, frac_bits,
+                                             c(cw.data_ptr()) if cw is not None else None, per, c(out.data_ptr()), t,
+                                             c(ovf.data_ptr()), c(logw.data_ptr()),
+                                             c(torch.cuda.current_stream(device).cuda_stream or None)))
+    return out, logw, ovf
+
+
+def _biased_sim(decoders, snr, sigma, collective, bias, harvest, kw):
+    """The decoders' <family>_ber_sim_biased over them; harvest is None, a Harvest or max_records for a new one."""
+    hv = None
+    if harvest is not None:
+        hv = harvest if isinstance(harvest, Harvest) else Harvest(decoders[0].code, int(harvest))
+        hv._refresh()
+    p, keep = sim_params(snr, sigma, **kw)
+    hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
+    r = SimResult()
+    used = ctypes.c_int32(0)
+    _check(decoders[0]._fn("ber_sim_biased")(hs, len(decoders), ctypes.byref(p), collective, bias._h,
+                                             hv._h if hv is not None else None, ctypes.byref(r), ctypes.byref(used)))
+    del keep
+    out = {k: getattr(r, k) for k, _ in SimResult._fields_}
+    out["bias"] = bias
+    if hv is not None:
+        out["harvest"] = hv
+    return out, used.value
+
+
+def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
     host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
     The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix).
-    harvest as in Decoder.ber_sim."""
+    harvest and bias as in Decoder.ber_sim."""
     kinds = {type(d) for d in decoders}
     if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
         raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
+    if bias is not None:
+        out, used = _biased_sim(decoders, snr, sigma, collective, bias, harvest, kw)
+        out["collective"] = used
+        return out
     if harvest is not None:
         out, used = _harvest_sim(decoders, snr, sigma, collective, harvest, kw)
         out["collective"] = used

@@ -9,6 +9,7 @@
 #include <thread>
 #include <vector>
 
+#include "fpldpc_bias.hpp"
 #include "fpldpc_internal.hpp"
 
 // Bit parity with the gcc/glibc-built reference needs the exact operation sequence: no FMA
@@ -91,6 +92,70 @@ int fpldpc_channel_llr_host(int64_t seed, int64_t first_frame, int32_t frames, i
                     static_cast<int16_t *>(out)[at] = (int16_t)q;
                 }
             }
+    };
+    if (T == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < T; t++) th.emplace_back(work, t);
+        for (auto &x : th) x.join();
+    }
+    for (int t = 0; t < T; t++)
+        if (overflow[t]) return fpldpc::fail(FPLDPC_ERR_ARG, "LLR does not fit int16");
+    return FPLDPC_OK;
+}
+
+// The host twin of fpldpc_bias_channel_llr (fpldpc_bias.hip): the channel above with the mean shifted on the
+// bias's positions, and each frame's log-weight summed over them in ascending j.
+int fpldpc_bias_channel_llr_host(fpldpc_bias_t b, int64_t seed, int64_t first_frame, int32_t frames, double snr, double sigma,
+                                 int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame, void *out, int32_t out_type,
+                                 double *logw, int32_t nthreads) {
+    if (!b) return fpldpc::fail(FPLDPC_ERR_ARG, "bias: null bias");
+    if (!out || frames < 0 || first_frame < 0 || frac_bits < 0 || frac_bits > 24 || seed <= 0 || seed >= kModulus)
+        return fpldpc::fail(FPLDPC_ERR_ARG, "bias: bad channel arguments");
+    if (out_type != FPLDPC_LLR_I32 && out_type != FPLDPC_LLR_I16 && out_type != FPLDPC_LLR_F64)
+        return fpldpc::fail(FPLDPC_ERR_ARG, "bias: bad out_type");
+    if (cw_per_frame != 0 && cw_per_frame != 1) return fpldpc::fail(FPLDPC_ERR_ARG, "bias: cw_per_frame must be 0 or 1");
+    if (frames == 0) return FPLDPC_OK;
+    const int n = b->n, count = b->count();
+    unsigned hw = std::thread::hardware_concurrency();
+    int T = nthreads > 0 ? nthreads : (int)(hw ? hw : 1);
+    T = std::max(1, std::min(T, frames));
+    std::vector<int> overflow(T, 0);
+    auto work = [&](int t) {
+        const int64_t f_lo = (int64_t)frames * t / T, f_hi = (int64_t)frames * (t + 1) / T;
+        int64_t state = fpldpc_rng_skip(seed, (uint64_t)(first_frame + f_lo) * (uint64_t)n);
+        const double scale = (double)(1 << frac_bits);
+        for (int64_t f = f_lo; f < f_hi; f++) {
+            const uint8_t *c = cw ? cw + (cw_per_frame ? (size_t)f * n : 0) : nullptr;
+            double sum = 0.0;
+            int j = 0;
+            for (int i = 0; i < n; i++) {
+                const int s = 1 - 2 * (c ? (int)(c[i] & 1) : 0);
+                const double nrm = odeh_evans_normal(&state, sigma);
+                double llr;
+                if (j < count && b->pos[j] == i) {
+                    const double a = b->shift[j++];
+                    llr = (2 * snr) * (s * (1 - a) + nrm);
+                    sum = sum + a * (2 * s * nrm - a) / (2 * sigma * sigma);
+                } else {
+                    llr = 2 * snr * (s + nrm);
+                }
+                const size_t at = (size_t)f * n + i;
+                if (out_type == FPLDPC_LLR_F64) {
+                    static_cast<double *>(out)[at] = llr;
+                    continue;
+                }
+                const int32_t q = (int32_t)(llr * scale);  // int() truncation, no clipping
+                if (out_type == FPLDPC_LLR_I32) {
+                    static_cast<int32_t *>(out)[at] = q;
+                } else {
+                    if (q < -32768 || q > 32767) overflow[t] = 1;
+                    static_cast<int16_t *>(out)[at] = (int16_t)q;
+                }
+            }
+            if (logw) logw[f] = sum;
+        }
     };
     if (T == 1) {
         work(0);

@@ -31,6 +31,13 @@
 // unsat) and err / syn row, the ordered compaction gathers the codeword-error frames' rows behind the pairs, and
 // one copy takes both to pinned memory.  After the stop decision rank 0's thread appends the ranks' chunks to the harvest in frame
 // order up to the stop frame, where on_frame is called.  Without a harvest none of this exists.
+//
+// Bias (the *_ber_sim_biased entry points; fpldpc_bias.hip): each slot has the chunk's log-weights on the device
+// and a pinned twin.  The patch kernel follows the slot's channel launch, before the forced positions are
+// written; the copy goes with the slot's other copies, before `done`.  In the frame-order loop that serves
+// on_frame and the harvest, rank 0's thread adds the weighted sums (include/fpldpc.h, fpldpc_bias_sums) up to
+// and including the stop frame: they depend on neither the chunk size nor the number of ranks.  Without a bias
+// none of this exists.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -47,6 +54,9 @@
 #include <thread>
 #include <vector>
 
+#include <cmath>
+
+#include "fpldpc_bias.hpp"
 #include "fpldpc_harvest.hpp"
 #include "fpldpc_internal.hpp"
 #include "fpldpc_layered.hpp"
@@ -110,6 +120,8 @@ struct Slot {
     // [chunk][row words] and the compaction's scratch [chunk] stay on the device
     int32_t *d_hv = nullptr, *h_hv = nullptr, *d_pos = nullptr;
     uint32_t *d_rows = nullptr;
+    // bias: the chunk's log-weights [chunk] and their pinned twin
+    double *d_logw = nullptr, *h_logw = nullptr;
 };
 
 // One rank: a decoder, its stream, two chunk slots.
@@ -130,6 +142,9 @@ struct Rank {
     uint16_t *d_table = nullptr;   // this device's copy of its check table
     uint8_t *d_hv_cw = nullptr;    // the fixed codeword [n] on the device where the host channel keeps it on the host
     int cap = 0, row_words = 0;    // records per chunk buffer, words per record row (err | syn)
+    const fpldpc_bias *bias = nullptr;  // bias: the shift of this simulation's channel, or null
+    int32_t *d_bias_pos = nullptr;      // this device's copy of its positions and shifts
+    double *d_bias_shift = nullptr;
     ~Rank() {
         // a rank that left early (an error) may still have a chunk in flight: let it finish before
         // its buffers and the twin decoder go
@@ -141,7 +156,11 @@ struct Rank {
         (void)hipFree(d_info_idx);
         (void)hipFree(d_table);
         (void)hipFree(d_hv_cw);
+        (void)hipFree(d_bias_pos);
+        (void)hipFree(d_bias_shift);
         for (auto &x : s) {
+            (void)hipFree(x.d_logw);
+            (void)hipHostFree(x.h_logw);
             (void)hipFree(x.d_hv);
             (void)hipFree(x.d_pos);
             (void)hipFree(x.d_rows);
@@ -188,6 +207,14 @@ struct Rank {
         if (hv) {
             int st = setup_harvest();
             if (st) return st;
+        }
+        if (bias) {
+            int st = bias_upload_tables(*bias, &d_bias_pos, &d_bias_shift);
+            if (st) return st;
+            for (auto &x : s) {
+                HIP_TRY(hipMalloc((void **)&x.d_logw, (size_t)chunk * sizeof(double)));
+                HIP_TRY(hipHostMalloc((void **)&x.h_logw, (size_t)chunk * sizeof(double), hipHostMallocDefault));
+            }
         }
         if (sp->random_info) return setup_source();
         if (sp->count_mode == FPLDPC_COUNT_BITS) {
@@ -289,6 +316,10 @@ struct Rank {
                                     sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf,
                                     st)))
                 return r;
+            if (bias && (r = launch_bias_patch(*bias, d_bias_pos, d_bias_shift, sp->seed, x.first, (int)x.frames, sp->snr,
+                                               sp->sigma, sp->frac_bits, sp->random_info ? x.d_cw : d_cw,
+                                               sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf, x.d_logw, st)))
+                return r;
             if (sp->n_forced > 0 &&
                 (r = launch_force_llr(x.d_llr, (int)x.frames, n, d_forced, sp->n_forced, (int16_t)sp->forced_llr, st)))
                 return r;
@@ -304,6 +335,7 @@ struct Rank {
             (r = launch_count_info(x.d_hard, (n + 31) / 32, d_info_idx, x.d_info, k, (int)x.frames, x.d_out, st)))
             return r;
         if (hv && (r = submit_harvest(x, st))) return r;
+        if (bias) HIP_TRY(hipMemcpyAsync(x.h_logw, x.d_logw, (size_t)x.frames * sizeof(double), hipMemcpyDeviceToHost, st));
         if (count_bits)
             HIP_TRY(hipMemcpyAsync(x.h_out, x.d_out, (size_t)x.frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(x.h_out + chunk, x.d_out + chunk, (size_t)x.frames * sizeof(int32_t),
@@ -465,6 +497,8 @@ struct Shared {
     Exchange *ex = nullptr;
     std::vector<Rank *> ranks;  // on_frame, harvest: rank 0's thread reads every rank's slot in frame order
     fpldpc_harvest *hv = nullptr;
+    bool biased = false;       // a bias: rank 0's thread adds the weighted sums in frame order
+    fpldpc_bias_sums wsums{};
     // per rank outcome
     std::vector<int> status;
     std::vector<std::string> message;
@@ -552,7 +586,7 @@ int rank_loop(Shared &sh, int rank) {
         std::vector<plan::Sums> sums(ndev);
         for (int i = 0; i < ndev; ++i) sums[i] = unpack(&all[(size_t)i * kWords]);
         const int sr = plan::stop_rank(sums.data(), ndev, total.frame_errors, need);
-        if (sp->on_frame || sh.hv) {  // frame order across ranks: rank 0's thread calls back and harvests for everyone
+        if (sp->on_frame || sh.hv || sh.biased) {  // frame order across ranks: rank 0's thread calls back and harvests for everyone
             if (!sh.ex->bar.wait()) return fail(FPLDPC_ERR_HIP, "another rank of the simulation failed");
             if (rank == 0) {
                 plan::Sums run = total;
@@ -569,6 +603,22 @@ int rank_loop(Shared &sh, int rank) {
                             sh.hv->add_frame(xi.first + f, Ri.its(xi)[f], Ri.blk(xi)[f], w, xi.h_hv[xi.frames + f],
                                              keep ? recs + (size_t)rec * Ri.row_words : nullptr);
                             rec += w > 0;
+                        }
+                        if (sh.biased) {
+                            const double lw = xi.h_logw[f], w = exp(lw);
+                            const int64_t blk = Ri.blk(xi)[f];
+                            const double fe = blk > 0 ? 1.0 : 0.0;
+                            fpldpc_bias_sums &b = sh.wsums;
+                            ++b.frames;
+                            b.frame_errors += blk > 0;
+                            b.bit_errors += blk;
+                            b.sum_w += w;
+                            b.sum_w2 += w * w;
+                            b.sum_w_fe += w * fe;
+                            b.sum_w2_fe += w * w * fe;
+                            b.sum_w_be += w * (double)blk;
+                            b.min_logw = std::min(b.min_logw, lw);
+                            b.max_logw = std::max(b.max_logw, lw);
                         }
                         run.add_frame(Ri.blk(xi)[f], Ri.its(xi)[f]);
                         if (i == sr && need > 0 && run.frame_errors >= need) break;
@@ -641,12 +691,26 @@ int validate(const Dec &dec, const fpldpc_sim_params *sp) {
     return FPLDPC_OK;
 }
 
-// hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error
+// The rules a bias adds to a simulation's (include/fpldpc.h, fpldpc_ber_sim_biased)
+int validate_bias(const Dec &dec, const fpldpc_sim_params *sp, const fpldpc_bias &b) {
+    if (sp->device_channel != 1)
+        return fail(FPLDPC_ERR_ARG, "a bias needs device_channel = 1 (the host channel's path is not biased)");
+    if (sp->count_mode != FPLDPC_COUNT_BITS) return fail(FPLDPC_ERR_ARG, "a bias needs count_mode = FPLDPC_COUNT_BITS");
+    if (b.n != dec.code().n) return fail(FPLDPC_ERR_ARG, "the bias was made for another n than the decoders' code");
+    for (int i = 0; i < sp->n_forced; i++)
+        if (std::binary_search(b.pos.begin(), b.pos.end(), sp->forced_index[i]))
+            return fail(FPLDPC_ERR_ARG, "a forced position is also a biased one (bias and shortening must not overlap)");
+    return FPLDPC_OK;
+}
+
+// hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error.
+// bias: the shift of the channel; a *_ber_sim_biased call (biasing) without one is an error
 int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used,
-            fpldpc_harvest *hv = nullptr, bool harvesting = false) {
+            fpldpc_harvest *hv = nullptr, bool harvesting = false, fpldpc_bias *bias = nullptr, bool biasing = false) {
     const int ndev = (int)dv.size();
     if (ndev < 1 || !sp || !out) return fail(FPLDPC_ERR_ARG, "null argument");
     if (harvesting && !hv) return fail(FPLDPC_ERR_ARG, "null harvest");
+    if (biasing && !bias) return fail(FPLDPC_ERR_ARG, "null bias");
     if (hv && sp->count_mode != FPLDPC_COUNT_BITS)
         return fail(FPLDPC_ERR_ARG, "a harvest needs count_mode = FPLDPC_COUNT_BITS");
     if (collective < FPLDPC_COLL_AUTO || collective > FPLDPC_COLL_HOST) return fail(FPLDPC_ERR_ARG, "bad collective");
@@ -661,11 +725,13 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         }
         int st = validate(dv[i], sp);
         if (st) return st;
+        if (bias && (st = validate_bias(dv[i], sp, *bias))) return st;
         const fpldpc_code &c = dv[i].code();
         if (hv && (hv->n != c.n || hv->m != c.m || hv->dc != c.dc_max || hv->clist != c.clist))
             return fail(FPLDPC_ERR_ARG, "the harvest was made from another code than the decoders'");
     }
     if (hv) hv->clear();
+    if (bias) bias->sums = fpldpc_bias_sums{};
     static_assert(FPLDPC_COLL_AUTO == plan::kCollAuto && FPLDPC_COLL_RCCL == plan::kCollRccl &&
                   FPLDPC_COLL_HOST == plan::kCollHost, "collective codes");
     // (test hook: comm_init == 2 makes AUTO attempt RCCL with a single decoder, so that its fallback
@@ -681,6 +747,9 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
     Shared sh;
     sh.sp = sp;
     sh.hv = hv;
+    sh.biased = bias != nullptr;
+    sh.wsums.min_logw = INFINITY;
+    sh.wsums.max_logw = -INFINITY;
     sh.ndev = ndev;
     sh.chunk = sp->chunk > 0 ? sp->chunk : 16384;
     if (sp->max_frames > 0) sh.chunk = (int)std::min<int64_t>(sh.chunk, sp->max_frames);
@@ -696,6 +765,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         ranks[i]->n = dv[i].code().n;
         ranks[i]->overlap = overlap;
         ranks[i]->hv = hv;
+        ranks[i]->bias = bias;
         if (hipSetDevice(dv[i].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         int st = ranks[i]->setup();
         if (st) return st;
@@ -749,6 +819,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
     r.frames_decoded = sh.decoded;
     r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     *out = r;
+    if (bias) bias->sums = sh.wsums;
     if (used) *used = coll_used;  // what ran, after any AUTO fallback
     return FPLDPC_OK;
 }
@@ -831,6 +902,23 @@ int fpldpc_minsum_ber_sim_harvest(const fpldpc_minsum_t *decs, int32_t ndev, con
                                   int32_t collective, fpldpc_harvest_t h, fpldpc_sim_result *out,
                                   int32_t *collective_used) {
     return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, true);
+}
+
+int fpldpc_ber_sim_biased(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                          fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, true);
+}
+
+int fpldpc_layered_ber_sim_biased(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                  int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, true);
+}
+
+int fpldpc_minsum_ber_sim_biased(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                 int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, true);
 }
 
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init) {

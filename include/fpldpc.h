@@ -577,6 +577,85 @@ int fpldpc_harvest_records(fpldpc_harvest_t h, int64_t first, int64_t count, int
 int fpldpc_harvest_classes(fpldpc_harvest_t h, int32_t *weight, int32_t *unsat, int64_t *count, int32_t cap,
                            int32_t *n_classes);
 
+/* ---------------------------------------------------------------- importance sampling: a shifted mean */
+/* What the harvest cannot say (no reference counterpart): how often a structure it found costs a frame at an
+ * Eb/N0 where plain simulation sees none.  Mean-shift importance sampling moves the transmitted amplitude on
+ * the positions of a suspected structure toward the wrong decision and weights every frame by the likelihood
+ * ratio between the true channel and the shifted one.
+ *
+ * A bias is n, count positions pos[j] (strictly ascending, 0 <= pos[j] < n, 0 <= count <= n) and count finite
+ * doubles a[j], the shift in units of the transmitted amplitude: a = 1 moves the mean to zero; negative and
+ * zero values are allowed.  For frame f and a position i outside the bias the LLR is fpldpc_channel_llr's, bit
+ * for bit.  For i = pos[j], with s = 1 - 2*cw[i], z the Odeh-Evans variate of draw f*n + i and
+ * nrm = 0.0 + sigma*z exactly as in that channel,
+ *     LLR     = (2*snr) * (s*(1 - a[j]) + nrm)            (each operation rounded once, no contraction)
+ *     LLR_fp  = (int)(LLR * 2^frac_bits)                  (I16 / I32 / F64 outputs as the channel's)
+ *     term_j  = a[j] * (2*s*nrm - a[j]) / (2*sigma*sigma)
+ *     logw[f] = sum_j term_j                              (double; 0.0 exactly when count = 0)
+ * The frame's weight w = exp(logw[f]) is the ratio of the true density N(s, sigma^2) to the shifted density
+ * N(s(1 - a), sigma^2) at the received values.  sigma is the noise deviation passed in; snr only scales the
+ * LLR, as in the channel.
+ *   - The reference's variates come from a 31-bit uniform, so |z| is bounded near 6.2: the weight is exact for
+ *     the Gaussian the stream approximates, not for its truncation.
+ *   - One call carries one bias.  Mixing biases and multiplying by orbit sizes is the caller's arithmetic.
+ * Host only, no GPU: copies pos and shift.  FPLDPC_ERR_ARG, with a message naming the rule, for n <= 0,
+ * count < 0 or count > n, a position out of range, unsorted or duplicate positions, a non-finite shift. */
+typedef struct fpldpc_bias *fpldpc_bias_t;
+int fpldpc_bias_create(int32_t n, const int32_t *pos, const double *shift, int32_t count, fpldpc_bias_t *out);
+void fpldpc_bias_free(fpldpc_bias_t b);
+/* dims = n, count */
+int fpldpc_bias_dims(fpldpc_bias_t b, int32_t dims[2]);
+/* The shifted channel on the host: fpldpc_channel_llr_host's arguments with n the bias's, cw uint8[n]
+ * (cw_per_frame = 0) or uint8[frames][n] (cw_per_frame = 1), NULL = all-zero, and logw double[frames]
+ * (may be NULL), term_j summed in ascending j.  The argument rules and the int16 rule (FPLDPC_ERR_ARG if a
+ * stored value does not fit, whether the shift put it there or not) are that channel's. */
+int fpldpc_bias_channel_llr_host(fpldpc_bias_t b, int64_t seed, int64_t first_frame, int32_t frames, double snr,
+                                 double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame, void *out,
+                                 int32_t out_type, double *logw, int32_t nthreads);
+/* The same on the device, asynchronous on `stream`: fpldpc_channel_llr's arguments with n the bias's, every
+ * pointer device memory, logw double[frames] (may be NULL).  It is fpldpc_channel_llr followed, on the same
+ * stream, by a patch kernel over the biased positions: a wave per frame, each lane summing its term_j in
+ * ascending j and the 64 lane sums reduced in a fixed order, so that the same call gives the same logw bits
+ * every time (no floating-point atomic); against the host's, logw differs by the summation order and the device
+ * libm's log (tests/test_gpu_bias_channel.py: within 1e-12 * (sum_j |term_j| + 1)).  *overflow counts the values
+ * actually stored outside int16, as the channel's: where the shifted value overflows and the unshifted one
+ * does not, or the other way round, the count follows the stored value.  The bias binds to the current device
+ * on first use (uploads positions and shifts), like a harvest. */
+int fpldpc_bias_channel_llr(fpldpc_bias_t b, int64_t seed, int64_t first_frame, int32_t frames, double snr,
+                            double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame, void *out,
+                            int32_t out_type, int32_t *overflow, double *logw, void *stream);
+/* The weighted sums of a biased simulation over its counted frames, first_frame up to and including the stop
+ * frame, added in frame order with w = exp(logw[f]), blk the frame's blkerror and fe = (blk > 0):
+ *     sum_w += w;  sum_w2 += w*w;  sum_w_fe += w*fe;  sum_w2_fe += w*w*fe;  sum_w_be += w*blk
+ * and the extremes of logw.  frames, frame_errors and bit_errors are the result's unweighted counts.  The order
+ * is the frame order whatever the chunk size and the number of ranks, so the sums depend on neither.
+ * sum_w_fe / frames estimates the frame error rate, sum_w_be / (frames * k) the bit error rate. */
+typedef struct {
+    int64_t frames, frame_errors, bit_errors;
+    double sum_w, sum_w2, sum_w_fe, sum_w2_fe, sum_w_be, min_logw, max_logw;
+} fpldpc_bias_sums;
+/* The simulation on the shifted channel: the _multi signatures plus b and h (h may be NULL: no harvest; else as
+ * the *_ber_sim_harvest calls); ndev = 1 with FPLDPC_COLL_HOST is the single form.  Per chunk, on the slot's
+ * stream, the patch kernel follows the channel kernel and runs before the forced positions are written; the
+ * chunk's logw is copied with the slot's other results.  After the stop decision one thread walks the ranks'
+ * chunks in frame order up to and including the stop frame and adds the sums above; a chunk decoded past the
+ * stop frame is drained and not added.  The stop rule, the fpldpc_sim_result (frame_errors stays the
+ * unweighted count), the on_frame sequence and the harvest keep their definitions, on the shifted channel's
+ * LLRs.  It works with random_info, with a fixed codeword and with the all-zero one.  FPLDPC_ERR_ARG, with a
+ * message naming the bias, if b is NULL, device_channel != 1, count_mode != FPLDPC_COUNT_BITS, b's n is not
+ * the code's, or a forced position is also a biased one; every other rule is as before.  b's sums are zeroed
+ * when the call starts and set when it returns FPLDPC_OK. */
+int fpldpc_ber_sim_biased(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                          fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out, int32_t *collective_used);
+int fpldpc_layered_ber_sim_biased(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                  int32_t *collective_used);
+int fpldpc_minsum_ber_sim_biased(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                                 int32_t *collective_used);
+/* Of the last simulation run with b (all zero before the first). */
+int fpldpc_bias_sums_get(fpldpc_bias_t b, fpldpc_bias_sums *out);
+
 #ifdef __cplusplus
 }
 #endif
