@@ -45,6 +45,8 @@ SOURCES = [
     "fpldpc_harvest.hip",
     # mean-shift importance sampling (the bias object and the patch kernel behind the channel's): outside the build id too
     "fpldpc_bias.hip",
+    # the counter-based noise source (the Philox channel kernel and its patch kernel for a bias): outside the build id too
+    "fpldpc_source.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

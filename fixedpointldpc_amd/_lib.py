@@ -152,6 +152,21 @@ SIGNATURES = {
     "fpldpc_minsum_ber_sim_biased": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, P, P,
                                                     ctypes.POINTER(SimResult), P]),
     "fpldpc_bias_sums_get": (ctypes.c_int, [P, ctypes.POINTER(BiasSums)]),
+    "fpldpc_philox4x32": (None, [P, P, P]),
+    "fpldpc_channel_llr_src_host": (ctypes.c_int, [I32, I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, P,
+                                                   I32, I32]),
+    "fpldpc_channel_llr_src": (ctypes.c_int, [I32, I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P,
+                                              I32, P, P]),
+    "fpldpc_bias_channel_llr_src_host": (ctypes.c_int, [P, I32, I64, I64, I32, ctypes.c_double, ctypes.c_double, I32, P,
+                                                        I32, P, I32, P, I32]),
+    "fpldpc_bias_channel_llr_src": (ctypes.c_int, [P, I32, I64, I64, I32, ctypes.c_double, ctypes.c_double, I32, P, I32, P,
+                                                   I32, P, P, P]),
+    "fpldpc_ber_sim_source": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, I32, P, P, ctypes.POINTER(SimResult),
+                                             P]),
+    "fpldpc_layered_ber_sim_source": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, I32, P, P,
+                                                     ctypes.POINTER(SimResult), P]),
+    "fpldpc_minsum_ber_sim_source": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, I32, P, P,
+                                                    ctypes.POINTER(SimResult), P]),
     "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
     "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
     "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
@@ -289,7 +304,7 @@ class Code:
 def _entries(family, **irregular):
     """A decoder class's entry points: <family>_<method>, except where the ABI names them otherwise."""
     names = ("destroy", "describe", "set_reference", "decode", "decode_host", "ber_sim", "ber_sim_multi", "ber_sim_harvest",
-             "ber_sim_biased")
+             "ber_sim_biased", "ber_sim_source")
     return {**{k: f"{family}_{k}" for k in names}, **irregular}
 
 
@@ -396,13 +411,17 @@ class _DecoderBase:
             out["totals"] = tot
         return out
 
-    def ber_sim(self, snr, sigma, harvest=None, bias=None, **kw):
+    def ber_sim(self, snr, sigma, harvest=None, bias=None, source="lehmer", **kw):
         """Ordered BER/FER simulation around this decoder (fpldpc_ber_sim, fpldpc_layered_ber_sim,
         fpldpc_minsum_ber_sim): the reference harness's frame loop, batched.
         Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
         patterns (<family>_ber_sim_harvest), the filled Harvest under the result's "harvest" key.
         bias = a Bias: the simulation on the shifted channel (<family>_ber_sim_biased, with or without a
-        harvest), the Bias with its weighted sums under the result's "bias" key."""
+        harvest), the Bias with its weighted sums under the result's "bias" key.
+        source = "lehmer" (the reference's stream, the entry points above) or "philox" (the counter-based noise
+        source, <family>_ber_sim_source, with or without a bias and a harvest); ValueError on anything else."""
+        if _source(source) != FPLDPC_NOISE_LEHMER:
+            return _source_sim([self], snr, sigma, FPLDPC_COLL_HOST, source, bias, harvest, kw)[0]
         if bias is not None:
             return _biased_sim([self], snr, sigma, FPLDPC_COLL_HOST, bias, harvest, kw)[0]
         if harvest is not None:
@@ -628,26 +647,59 @@ def info_bits_ptrs(info_seed, first_frame, frames, k, out_ptr, stream=0):
     _check(lib().fpldpc_info_bits(info_seed, first_frame, frames, k, out_ptr, stream or None))
 
 
-def channel_llr(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0):
-    """Reference-harness LLRs (PerfTest.cpp:108-120) for frames [first_frame, first_frame+frames)."""
+FPLDPC_NOISE_LEHMER, FPLDPC_NOISE_PHILOX = 0, 1
+_SOURCES = {"lehmer": FPLDPC_NOISE_LEHMER, "philox": FPLDPC_NOISE_PHILOX}
+
+
+def _source(source):
+    """The noise source's code (include/fpldpc.h) of "lehmer" or "philox"."""
+    if not isinstance(source, str) or source not in _SOURCES:
+        raise ValueError(f'source must be "lehmer" or "philox", not {source!r}')
+    return _SOURCES[source]
+
+
+def philox4x32(ctr, key):
+    """Philox4x32-10 (fpldpc_philox4x32) of a counter (4 words) under a key (2 words): uint32 [4]."""
+    c = np.ascontiguousarray(ctr, np.uint32).reshape(4)
+    k = np.ascontiguousarray(key, np.uint32).reshape(2)
+    out = np.empty(4, np.uint32)
+    lib().fpldpc_philox4x32(_ptr(c), _ptr(k), _ptr(out))
+    return out
+
+
+def channel_llr(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0,
+                source="lehmer"):
+    """Reference-harness LLRs (PerfTest.cpp:108-120) for frames [first_frame, first_frame+frames); source = "philox":
+    the same channel on the counter-based noise source (fpldpc_channel_llr_src_host)."""
     out = np.empty((frames, n), dtype)
     t = {np.dtype(np.int16): FPLDPC_LLR_I16, np.dtype(np.int32): FPLDPC_LLR_I32,
          np.dtype(np.float64): FPLDPC_LLR_F64}[np.dtype(dtype)]
     cwa = None if cw is None else np.ascontiguousarray(cw, np.uint8)
+    if _source(source) != FPLDPC_NOISE_LEHMER:
+        _check(lib().fpldpc_channel_llr_src_host(_source(source), seed, first_frame, frames, n, snr, sigma, frac_bits,
+                                                 _ptr(cwa), _ptr(out), t, nthreads))
+        return out
     _check(lib().fpldpc_channel_llr_host(seed, first_frame, frames, n, snr, sigma, frac_bits, _ptr(cwa), _ptr(out), t,
                                          nthreads))
     return out
 
 
 def channel_llr_ptrs(seed, first_frame, frames, n, snr, sigma, frac_bits, cw_ptr, cw_per_frame, out_ptr, out_type,
-                     overflow_ptr=0, stream=0):
-    """Device channel (async on `stream`); every pointer is device memory (0 = NULL)."""
+                     overflow_ptr=0, stream=0, source="lehmer"):
+    """Device channel (async on `stream`); every pointer is device memory (0 = NULL).  source as channel_llr
+    (fpldpc_channel_llr_src)."""
+    if _source(source) != FPLDPC_NOISE_LEHMER:
+        _check(lib().fpldpc_channel_llr_src(_source(source), seed, first_frame, frames, n, snr, sigma, frac_bits,
+                                            cw_ptr or None, cw_per_frame, out_ptr, out_type, overflow_ptr or None,
+                                            stream or None))
+        return
     _check(lib().fpldpc_channel_llr(seed, first_frame, frames, n, snr, sigma, frac_bits, cw_ptr or None, cw_per_frame,
                                     out_ptr, out_type, overflow_ptr or None, stream or None))
 
 
-def channel_llr_torch(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=None, dtype=None, device=None):
-    """Device channel into a new torch [frames, n] tensor (int16 default) on torch's current stream.
+def channel_llr_torch(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=None, dtype=None, device=None,
+                      source="lehmer"):
+    """Device channel into a new torch [frames, n] tensor (int16 default) on torch's current stream; source as channel_llr.
     cw: None, a uint8 [n] tensor (shared) or [frames, n] (per frame).  Returns (llr, overflow) -- overflow: int32 [1] count of values outside int16."""
     import torch
     dtype = dtype or torch.int16
@@ -661,8 +713,9 @@ def channel_llr_torch(seed, first_frame, frames, n, snr, sigma, frac_bits=4, cw=
         per = 1 if cw.dim() == 2 else 0
         assert cw.shape[-1] == n and (not per or cw.shape[0] == frames)
     t = {torch.int16: FPLDPC_LLR_I16, torch.int32: FPLDPC_LLR_I32, torch.float64: FPLDPC_LLR_F64}[dtype]
+    _source(source)
     channel_llr_ptrs(seed, first_frame, frames, n, snr, sigma, frac_bits, cw.data_ptr() if cw is not None else 0, per,
-                     out.data_ptr(), t, ovf.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+                     out.data_ptr(), t, ovf.data_ptr(), torch.cuda.current_stream(device).cuda_stream, source=source)
     return out, ovf
 
 
@@ -873,23 +926,34 @@ class Bias:
 _LLR_TYPES = {np.dtype(np.int16): FPLDPC_LLR_I16, np.dtype(np.int32): FPLDPC_LLR_I32, np.dtype(np.float64): FPLDPC_LLR_F64}
 
 
-def channel_llr_biased(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0):
+def channel_llr_biased(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=np.int16, nthreads=0,
+                       source="lehmer"):
     """The shifted channel on the host (fpldpc_bias_channel_llr_host) for frames [first_frame, first_frame + frames);
-    cw: None, uint8 [n] (shared) or [frames][n] (per frame).  Returns (llr [frames][n], logw [frames])."""
+    cw: None, uint8 [n] (shared) or [frames][n] (per frame).  Returns (llr [frames][n], logw [frames]).
+    source as channel_llr (fpldpc_bias_channel_llr_src_host)."""
+    src = _source(source)
     out = np.empty((frames, bias.n), dtype)
     logw = np.empty(frames, np.float64)
     cwa = None if cw is None else np.ascontiguousarray(cw, np.uint8)
     per = 1 if cwa is not None and cwa.ndim == 2 else 0
     assert cwa is None or (cwa.shape[-1] == bias.n and (not per or cwa.shape[0] == frames))
+    if src != FPLDPC_NOISE_LEHMER:
+        _check(lib().fpldpc_bias_channel_llr_src_host(bias._h, src, seed, first_frame, frames, snr, sigma, frac_bits,
+                                                      _ptr(cwa), per, _ptr(out), _LLR_TYPES[np.dtype(dtype)], _ptr(logw),
+                                                      nthreads))
+        return out, logw
     _check(lib().fpldpc_bias_channel_llr_host(bias._h, seed, first_frame, frames, snr, sigma, frac_bits, _ptr(cwa), per,
                                               _ptr(out), _LLR_TYPES[np.dtype(dtype)], _ptr(logw), nthreads))
     return out, logw
 
 
-def channel_llr_biased_torch(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=None, device=None):
+def channel_llr_biased_torch(bias, seed, first_frame, frames, snr, sigma, frac_bits=4, cw=None, dtype=None, device=None,
+                             source="lehmer"):
     """The shifted channel on the device (fpldpc_bias_channel_llr) into new torch tensors on torch's current stream;
-    arguments as channel_llr_torch.  Returns (llr [frames, n], logw float64 [frames], overflow int32 [1])."""
+    arguments as channel_llr_torch.  Returns (llr [frames, n], logw float64 [frames], overflow int32 [1]).
+    source as channel_llr (fpldpc_bias_channel_llr_src)."""
     import torch
+    src = _source(source)
     dtype = dtype or torch.int16
     device = torch.device(device if device is not None else (cw.device if cw is not None else "cuda"))
     out = torch.empty((frames, bias.n), dtype=dtype, device=device)
@@ -904,6 +968,12 @@ def channel_llr_biased_torch(bias, seed, first_frame, frames, snr, sigma, frac_b
     t = {torch.int16: FPLDPC_LLR_I16, torch.int32: FPLDPC_LLR_I32, torch.float64: FPLDPC_LLR_F64}[dtype]
     c = ctypes.c_void_p
     with torch.cuda.device(device):
+        if src != FPLDPC_NOISE_LEHMER:
+            _check(lib().fpldpc_bias_channel_llr_src(bias._h, src, seed, first_frame, frames, snr, sigma, frac_bits,
+                                                     c(cw.data_ptr()) if cw is not None else None, per, c(out.data_ptr()),
+                                                     t, c(ovf.data_ptr()), c(logw.data_ptr()),
+                                                     c(torch.cuda.current_stream(device).cuda_stream or None)))
+            return out, logw, ovf
         _check(lib().fpldpc_bias_channel_llr(bias._h, seed, first_frame, frames, snr, sigma, frac_bits,
                                              c(cw.data_ptr()) if cw is not None else None, per, c(out.data_ptr()), t,
                                              c(ovf.data_ptr()), c(logw.data_ptr()),
@@ -931,14 +1001,40 @@ def _biased_sim(decoders, snr, sigma, collective, bias, harvest, kw):
     return out, used.value
 
 
-def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, **kw):
+def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
+    """The decoders' <family>_ber_sim_source over them on `source`; bias is None or a Bias, harvest as in _biased_sim."""
+    hv = None
+    if harvest is not None:
+        hv = harvest if isinstance(harvest, Harvest) else Harvest(decoders[0].code, int(harvest))
+        hv._refresh()
+    p, keep = sim_params(snr, sigma, **kw)
+    hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
+    r = SimResult()
+    used = ctypes.c_int32(0)
+    _check(decoders[0]._fn("ber_sim_source")(hs, len(decoders), ctypes.byref(p), collective, _source(source),
+                                             bias._h if bias is not None else None, hv._h if hv is not None else None,
+                                             ctypes.byref(r), ctypes.byref(used)))
+    del keep
+    out = {k: getattr(r, k) for k, _ in SimResult._fields_}
+    if bias is not None:
+        out["bias"] = bias
+    if hv is not None:
+        out["harvest"] = hv
+    return out, used.value
+
+
+def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, source="lehmer", **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
     host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
     The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix).
-    harvest and bias as in Decoder.ber_sim."""
+    harvest, bias and source as in Decoder.ber_sim."""
     kinds = {type(d) for d in decoders}
     if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
         raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
+    if _source(source) != FPLDPC_NOISE_LEHMER:
+        out, used = _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw)
+        out["collective"] = used
+        return out
     if bias is not None:
         out, used = _biased_sim(decoders, snr, sigma, collective, bias, harvest, kw)
         out["collective"] = used

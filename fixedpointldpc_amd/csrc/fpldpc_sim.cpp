@@ -38,6 +38,10 @@
 // on_frame and the harvest, rank 0's thread adds the weighted sums (include/fpldpc.h, fpldpc_bias_sums) up to
 // and including the stop frame: they depend on neither the chunk size nor the number of ranks.  Without a bias
 // none of this exists.
+//
+// Source (the *_ber_sim_source entry points; fpldpc_source.hip): the three places that make noise -- generate, the
+// slot's channel launch and its patch launch -- take the noise source; every other entry point passes the Lehmer
+// stream and launches and allocates what it did before.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -62,6 +66,7 @@
 #include "fpldpc_layered.hpp"
 #include "fpldpc_sim_plan.hpp"
 #include "fpldpc_sim_source.hpp"
+#include "fpldpc_source.hpp"
 #include "fpldpc_testing.h"
 
 using namespace fpldpc;
@@ -145,6 +150,7 @@ struct Rank {
     const fpldpc_bias *bias = nullptr;  // bias: the shift of this simulation's channel, or null
     int32_t *d_bias_pos = nullptr;      // this device's copy of its positions and shifts
     double *d_bias_shift = nullptr;
+    int source = FPLDPC_NOISE_LEHMER;  // the noise source of generate, launch_channel and launch_bias_patch
     ~Rank() {
         // a rank that left early (an error) may still have a chunk in flight: let it finish before
         // its buffers and the twin decoder go
@@ -293,8 +299,8 @@ struct Rank {
         x.first = r.first;
         x.frames = r.frames;
         if (x.frames <= 0 || sp->device_channel) return FPLDPC_OK;
-        int st = fpldpc_channel_llr_host(sp->seed, x.first, (int32_t)x.frames, n, sp->snr, sp->sigma, sp->frac_bits,
-                                         sp->codeword, x.h_llr, FPLDPC_LLR_I16, sp->host_threads);
+        int st = fpldpc_channel_llr_src_host(source, sp->seed, x.first, (int32_t)x.frames, n, sp->snr, sp->sigma,
+                                             sp->frac_bits, sp->codeword, x.h_llr, FPLDPC_LLR_I16, sp->host_threads);
         if (st) return st;
         for (int64_t f = 0; f < x.frames; f++)
             for (int i = 0; i < sp->n_forced; i++) x.h_llr[(size_t)f * n + sp->forced_index[i]] = (int16_t)sp->forced_llr;
@@ -312,13 +318,13 @@ struct Rank {
                 if ((r = fpldpc_info_bits(sp->info_seed, x.first, (int32_t)x.frames, k, x.d_info, st))) return r;
                 if ((r = fpldpc_encoder_encode(x.enc, x.d_info, (int32_t)x.frames, x.d_cw, st))) return r;
             }
-            if ((r = launch_channel(sp->seed, x.first, (int)x.frames, n, sp->snr, sp->sigma, sp->frac_bits,
-                                    sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf,
-                                    st)))
+            if ((r = launch_channel_src(source, sp->seed, x.first, (int)x.frames, n, sp->snr, sp->sigma, sp->frac_bits,
+                                        sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16,
+                                        ovf, st)))
                 return r;
-            if (bias && (r = launch_bias_patch(*bias, d_bias_pos, d_bias_shift, sp->seed, x.first, (int)x.frames, sp->snr,
-                                               sp->sigma, sp->frac_bits, sp->random_info ? x.d_cw : d_cw,
-                                               sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf, x.d_logw, st)))
+            if (bias && (r = launch_bias_patch_src(source, *bias, d_bias_pos, d_bias_shift, sp->seed, x.first, (int)x.frames,
+                                                   sp->snr, sp->sigma, sp->frac_bits, sp->random_info ? x.d_cw : d_cw,
+                                                   sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf, x.d_logw, st)))
                 return r;
             if (sp->n_forced > 0 &&
                 (r = launch_force_llr(x.d_llr, (int)x.frames, n, d_forced, sp->n_forced, (int16_t)sp->forced_llr, st)))
@@ -705,10 +711,17 @@ int validate_bias(const Dec &dec, const fpldpc_sim_params *sp, const fpldpc_bias
 
 // hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error.
 // bias: the shift of the channel; a *_ber_sim_biased call (biasing) without one is an error
+// source: the noise source (include/fpldpc.h); the entry points without one pass the Lehmer stream
 int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collective, fpldpc_sim_result *out, int32_t *used,
-            fpldpc_harvest *hv = nullptr, bool harvesting = false, fpldpc_bias *bias = nullptr, bool biasing = false) {
+            fpldpc_harvest *hv = nullptr, bool harvesting = false, fpldpc_bias *bias = nullptr, bool biasing = false,
+            int source = FPLDPC_NOISE_LEHMER) {
     const int ndev = (int)dv.size();
     if (ndev < 1 || !sp || !out) return fail(FPLDPC_ERR_ARG, "null argument");
+    if (source != FPLDPC_NOISE_LEHMER && source != FPLDPC_NOISE_PHILOX)
+        return fail(FPLDPC_ERR_ARG, "bad noise source (FPLDPC_NOISE_LEHMER or FPLDPC_NOISE_PHILOX)");
+    if (source == FPLDPC_NOISE_PHILOX &&
+        (sp->seed < 0 || sp->first_frame < 0 || (sp->max_frames > 0 && sp->first_frame > INT64_MAX - sp->max_frames)))
+        return fail(FPLDPC_ERR_ARG, "philox: 0 <= seed and first_frame + max_frames < 2^63");
     if (harvesting && !hv) return fail(FPLDPC_ERR_ARG, "null harvest");
     if (biasing && !bias) return fail(FPLDPC_ERR_ARG, "null bias");
     if (hv && sp->count_mode != FPLDPC_COUNT_BITS)
@@ -766,6 +779,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         ranks[i]->overlap = overlap;
         ranks[i]->hv = hv;
         ranks[i]->bias = bias;
+        ranks[i]->source = source;
         if (hipSetDevice(dv[i].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         int st = ranks[i]->setup();
         if (st) return st;
@@ -919,6 +933,24 @@ int fpldpc_minsum_ber_sim_biased(const fpldpc_minsum_t *decs, int32_t ndev, cons
                                  int32_t collective, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
                                  int32_t *collective_used) {
     return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, true);
+}
+
+int fpldpc_ber_sim_source(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                          int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                          int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, false, source);
+}
+
+int fpldpc_layered_ber_sim_source(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                  fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, false, source);
+}
+
+int fpldpc_minsum_ber_sim_source(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                 fpldpc_sim_result *out, int32_t *collective_used) {
+    return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, false, source);
 }
 
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init) {

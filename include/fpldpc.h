@@ -375,6 +375,50 @@ int fpldpc_channel_llr(int64_t seed, int64_t first_frame, int32_t frames, int32_
                        double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame,
                        void *out, int32_t out_type, int32_t *overflow, void *stream);
 
+/* ---------------------------------------------------------------- noise sources */
+/* The Lehmer stream above is the reference's and stays the default of everything that makes noise.  Its period is
+ * 2^31 - 2 draws and frame f uses draws [f*n, (f+1)*n): at n = 2209 the stream wraps every 972,152 frames, at
+ * n = 1944 frames f and f + 119,304,647 receive identical noise, and nothing reports either; one 31-bit uniform
+ * per variate bounds |z| near 6.2.  FPLDPC_NOISE_PHILOX is a counter-based source beside it: the variate is a pure
+ * function of (seed, frame, position), no two frames share noise for any run length, and the uniforms carry 53
+ * bits.  Every entry point that takes a `source` accepts these two values; any other is FPLDPC_ERR_ARG. */
+#define FPLDPC_NOISE_LEHMER 0 /* the reference's stream; everything without a source argument */
+#define FPLDPC_NOISE_PHILOX 1
+/* Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments
+ * 0x9E3779B9, 0xBB67AE85.  One round maps (c0, c1, c2, c3) to
+ *     (hi(M1*c2) ^ c1 ^ k0,  lo(M1*c2),  hi(M0*c0) ^ c3 ^ k1,  lo(M0*c0));
+ * ten rounds, the key bumped after each.  For seed S (0 <= S < 2^63), frame f >= 0 and position i in [0, n):
+ *     key     = (S & 0xffffffff, S >> 32)
+ *     counter = (i >> 1, 0, f & 0xffffffff, f >> 32)     word 1 is a stream id: 0 = channel noise, others reserved
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter, key)
+ *     a = (r0 | r1 << 32) >> 11,   b = (r2 | r3 << 32) >> 11
+ *     u1 = (a + 1) * 2^-53  in (0, 1],   u2 = b * 2^-53  in [0, 1)
+ *     rad = sqrt(-2 ln u1)
+ *     z   = rad * cos(2 pi u2) for even i,   rad * sin(2 pi u2) for odd i        (|z| <= 8.58)
+ *     nrm = 0.0 + sigma * z;  LLR = (2*snr) * ((1 - 2*cw[i]) + nrm);  LLR_fp = (int)(LLR * 2^frac_bits)
+ * The last three operations and the I16 / I32 / F64 outputs are the Lehmer channel's exactly (each operation
+ * rounded once, no contraction, the int16 overflow rules).  One Philox call serves the two positions of a pair;
+ * with odd n the last pair's sine half is unused.  Frame indices are limited only by first_frame + frames < 2^63:
+ * there is no 2^48 rule and no period.  ln, sin and cos come from the C library of the side that runs (the device
+ * uses sincospi(2*u2), where 2*u2 is exact), so the transform is defined as the mathematical value: two
+ * implementations agree to a few ulps of z, an F64 output within 1e-12 * 2*snr * (1 + 9*sigma), a quantised one
+ * exactly except where LLR * 2^frac_bits lies that close to an integer (tests/philox_model.py).  The same device
+ * call always gives the same bits.
+ * The information bits of random_info (fpldpc_info_bits) stay on their Lehmer generator whatever the noise
+ * source: a repeated information word only repeats a codeword, and the code is linear.
+ * Host only: the primitive that replays a frame without this library's channel. */
+void fpldpc_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* fpldpc_channel_llr_host / fpldpc_channel_llr on `source`.  FPLDPC_NOISE_LEHMER: exactly those functions, under
+ * their argument rules.  FPLDPC_NOISE_PHILOX: 0 <= seed < 2^63, first_frame >= 0, first_frame + frames < 2^63,
+ * every other rule as before; the host result does not depend on nthreads or on how a frame range is split into
+ * calls. */
+int fpldpc_channel_llr_src_host(int32_t source, int64_t seed, int64_t first_frame, int32_t frames, int32_t n,
+                                double snr, double sigma, int32_t frac_bits, const uint8_t *cw, void *out,
+                                int32_t out_type, int32_t nthreads);
+int fpldpc_channel_llr_src(int32_t source, int64_t seed, int64_t first_frame, int32_t frames, int32_t n, double snr,
+                           double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame, void *out,
+                           int32_t out_type, int32_t *overflow, void *stream);
+
 /* ---------------------------------------------------------------- systematic encoder */
 /* Replaces FP_Encoder (ArrayLDPC_Encoder.cpp:22-225, decl ArrayLDPCMacro.h:179-214). */
 typedef struct fpldpc_encoder *fpldpc_encoder_t;
@@ -532,6 +576,7 @@ int fpldpc_minsum_ber_sim_multi(const fpldpc_minsum_t *decs, int32_t ndev, const
  *            sorted by weight, then by unsat; independent of max_records too.
  * A record's frame index is enough to replay it: fpldpc_info_bits (first_frame = frame, frames = 1), the
  * encoder and fpldpc_channel_llr (first_frame = frame, frames = 1) regenerate that frame's LLRs for any decoder.
+ * A simulation run on another noise source (fpldpc_ber_sim_source) is replayed with fpldpc_channel_llr_src and that source.
  *
  * Per chunk and on the slot's stream, after the decode (called with its hard output) and before the slot is
  * waited for: the scan kernel below over every frame, an ordered compaction of the codeword-error frames'
@@ -596,7 +641,8 @@ int fpldpc_harvest_classes(fpldpc_harvest_t h, int32_t *weight, int32_t *unsat, 
  * N(s(1 - a), sigma^2) at the received values.  sigma is the noise deviation passed in; snr only scales the
  * LLR, as in the channel.
  *   - The reference's variates come from a 31-bit uniform, so |z| is bounded near 6.2: the weight is exact for
- *     the Gaussian the stream approximates, not for its truncation.
+ *     the Gaussian the stream approximates, not for its truncation.  The *_src forms below take the source
+ *     argument: with FPLDPC_NOISE_PHILOX z is that source's variate at (f, pos[j]), |z| <= 8.58.
  *   - One call carries one bias.  Mixing biases and multiplying by orbit sizes is the caller's arithmetic.
  * Host only, no GPU: copies pos and shift.  FPLDPC_ERR_ARG, with a message naming the rule, for n <= 0,
  * count < 0 or count > n, a position out of range, unsorted or duplicate positions, a non-finite shift. */
@@ -655,6 +701,35 @@ int fpldpc_minsum_ber_sim_biased(const fpldpc_minsum_t *decs, int32_t ndev, cons
                                  int32_t *collective_used);
 /* Of the last simulation run with b (all zero before the first). */
 int fpldpc_bias_sums_get(fpldpc_bias_t b, fpldpc_bias_sums *out);
+
+/* ---------------------------------------------------------------- the noise source through bias and simulation */
+/* The shifted channel on `source` (noise sources, above): the formulas for LLR, term_j and logw are unchanged, z
+ * is the source's variate at (f, pos[j]).  FPLDPC_NOISE_LEHMER: exactly fpldpc_bias_channel_llr_host /
+ * fpldpc_bias_channel_llr.  FPLDPC_NOISE_PHILOX: that source's argument rules; on the device the Philox channel
+ * kernel is followed by a patch kernel of the same form (a wave per frame, a fixed summation order, no
+ * floating-point atomic). */
+int fpldpc_bias_channel_llr_src_host(fpldpc_bias_t b, int32_t source, int64_t seed, int64_t first_frame, int32_t frames,
+                                     double snr, double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame,
+                                     void *out, int32_t out_type, double *logw, int32_t nthreads);
+int fpldpc_bias_channel_llr_src(fpldpc_bias_t b, int32_t source, int64_t seed, int64_t first_frame, int32_t frames,
+                                double snr, double sigma, int32_t frac_bits, const uint8_t *cw, int32_t cw_per_frame,
+                                void *out, int32_t out_type, int32_t *overflow, double *logw, void *stream);
+/* The simulation on `source`: the *_ber_sim_biased signatures with the source after `collective`; b and h may each
+ * be NULL (no bias, no harvest).  sp->seed is read by the source's rule (FPLDPC_NOISE_PHILOX: 0 <= seed < 2^63,
+ * first_frame + max_frames < 2^63); every other rule, the result, on_frame, the harvest and the bias sums keep
+ * their definitions, in every mode: host or device channel, every codeword mode, forced positions,
+ * FPLDPC_SIM_OVERLAP=0, several ranks with either collective.  random_info's information bits stay on their
+ * Lehmer generator.  With FPLDPC_NOISE_LEHMER the call equals *_ber_sim_multi (b = h = NULL), *_ber_sim_harvest
+ * (b = NULL) or *_ber_sim_biased bit for bit. */
+int fpldpc_ber_sim_source(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp, int32_t collective,
+                          int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h, fpldpc_sim_result *out,
+                          int32_t *collective_used);
+int fpldpc_layered_ber_sim_source(const fpldpc_layered_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                  int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                  fpldpc_sim_result *out, int32_t *collective_used);
+int fpldpc_minsum_ber_sim_source(const fpldpc_minsum_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                 int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                 fpldpc_sim_result *out, int32_t *collective_used);
 
 #ifdef __cplusplus
 }
