@@ -96,6 +96,7 @@ SIGNATURES = {
     "fpldpc_layered_decode": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P, P]),
     "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
     "fpldpc_minsum_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, ctypes.POINTER(P)]),
+    "fpldpc_flood_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, ctypes.POINTER(P)]),
     "fpldpc_minsum_destroy": (ctypes.c_int, [P]),
     "fpldpc_minsum_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
     "fpldpc_minsum_set_reference": (ctypes.c_int, [P, P, P, I32]),
@@ -309,7 +310,7 @@ def _entries(family, **irregular):
 
 
 class _DecoderBase:
-    """What Decoder, LayeredDecoder and MinSumDecoder share: a handle made by the subclass's __init__ and the
+    """What Decoder, LayeredDecoder, MinSumDecoder and FloodSatDecoder share: a handle made by the subclass's __init__ and the
     methods every decoder object of the ABI has, through the class's table of entry-point names."""
 
     _ENTRY = {}
@@ -562,6 +563,23 @@ class MinSumDecoder(LayeredDecoder):
         p = self._params(max_iter=max_iter, early_term=early_term, precheck=precheck, device=device)
         h = ctypes.c_void_p()
         _check(lib().fpldpc_minsum_create(code._h, ctypes.byref(p), post_bits, msg_bits, scale_16, offset, ctypes.byref(h)))
+        self._adopt(code, h, p)
+
+
+class FloodSatDecoder(_DecoderBase):
+    """fpldpc_minsum_t of fpldpc_flood_create_sat: the reference's flooding schedule and sxor fold with
+    posteriors post_bits wide and messages msg_bits wide (int16 c2v per edge on chip), defined for every
+    input; where no clamp acts it is Decoder at the same frac_bits and width_mask bit for bit.  Check degrees
+    2..64 and the state in LDS only (FpldpcError -4 otherwise).  Same outputs and methods as MinSumDecoder,
+    whose entry points it runs through."""
+
+    _ENTRY = _entries("fpldpc_minsum")
+
+    def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
+                 post_bits=12, msg_bits=10):
+        p = self._params(max_iter, frac_bits, width_mask, early_term, precheck, device)
+        h = ctypes.c_void_p()
+        _check(lib().fpldpc_flood_create_sat(code._h, ctypes.byref(p), post_bits, msg_bits, ctypes.byref(h)))
         self._adopt(code, h, p)
 
 
@@ -1026,11 +1044,12 @@ def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
 def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, source="lehmer", **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
     host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
-    The decoders are all Decoder, all LayeredDecoder or all MinSumDecoder objects (ValueError on a mix).
+    The decoders are all Decoder, all LayeredDecoder, all MinSumDecoder or all FloodSatDecoder objects (ValueError on
+    a mix).
     harvest, bias and source as in Decoder.ber_sim."""
     kinds = {type(d) for d in decoders}
-    if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder}:
-        raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder or MinSumDecoder")
+    if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder, FloodSatDecoder}:
+        raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder, MinSumDecoder or FloodSatDecoder")
     if _source(source) != FPLDPC_NOISE_LEHMER:
         out, used = _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw)
         out["collective"] = used

@@ -50,7 +50,8 @@ int upload(fpldpc_layered *d) {
 // The three creation entry points (the arguments of the saturated and the min-sum decoder are validated
 // before anything touches HIP).
 // kFlood: the flooding min-sum decoder (fpldpc_minsum_create) over the same object; layer_checks unused.
-enum Kind { kUnsat, kSat, kMinsum, kFlood };
+// kFloodSxor: the saturated flooding decoder (fpldpc_flood_create_sat), likewise; scale_16 and offset unused.
+enum Kind { kUnsat, kSat, kMinsum, kFlood, kFloodSxor };
 
 int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, Kind kind, int32_t post_bits,
            int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out) {
@@ -80,8 +81,19 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
             return fail(FPLDPC_ERR_ARG, who + ": need 0 <= offset <= S_m (" + std::to_string(sat_limit(msg_bits)) + ")");
         mode = kind == kMinsum ? kLayMinsum : kFloodMinsum;
     }
+    if (kind == kFloodSxor) {
+        if (!(2 <= msg_bits && msg_bits < post_bits && post_bits <= 16))
+            return fail(FPLDPC_ERR_ARG, "saturated flooding decoder: need 2 <= msg_bits < post_bits <= 16");
+        // fpldpc_layered_create_sat's reason: a posterior pinned at S_p minus its own message (at most S_m + C) must
+        // keep its sign; S_m + C <= 32767 follows, so the per-edge state is int16
+        if (sat_limit(post_bits) <= sat_limit(msg_bits) + constant_c(p.frac_bits))
+            return fail(FPLDPC_ERR_ARG, "saturated flooding decoder: need S_p > S_m + C (2^(post_bits-1) - 1 > 2^(msg_bits-1) - 1 + " +
+                                            std::to_string(constant_c(p.frac_bits)) + ")");
+        mode = kFloodSat;
+    }
+    const bool flooding = kind == kFlood || kind == kFloodSxor;
     int L = code->m, layers = 1;  // flooding: every check of the frame in one step
-    st = kind == kFlood ? 0 : code_layering(*code, layer_checks, &L, &layers);
+    st = flooding ? 0 : code_layering(*code, layer_checks, &L, &layers);
     if (st) return st;
     int dev = -1;
     st = select_device(p.device, &dev);
@@ -101,9 +113,10 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
         d->scale_16 = scale_16;
         d->offset = offset;
     }
-    st = kind == kFlood    ? flood_minsum_choose(d->code, dev, &d->lc)
-         : kind == kMinsum ? layered_minsum_choose(d->code, L, dev, &d->lc)
-                           : layered_choose(d->code, L, dev, mode, &d->lc);
+    st = kind == kFlood       ? flood_minsum_choose(d->code, dev, &d->lc)
+         : kind == kFloodSxor ? flood_sat_choose(d->code, dev, &d->lc)
+         : kind == kMinsum    ? layered_minsum_choose(d->code, L, dev, &d->lc)
+                              : layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
     st = upload(d.get());
     if (st) return st;
@@ -150,6 +163,7 @@ int launch(const fpldpc_layered &dec, const DecodeBuffers &b, int32_t llr_type, 
     }
     if (dec.lc.mode == kLayMinsum) return layered_minsum_launch(dec.lc, a, dec.scale_16, dec.offset, stream);
     if (dec.lc.mode == kFloodMinsum) return flood_minsum_launch(dec.lc, a, dec.scale_16, dec.offset, stream);
+    if (dec.lc.mode == kFloodSat) return flood_sat_launch(dec.lc, a, stream);
     return layered_launch(dec.lc, a, stream);
 }
 
@@ -248,13 +262,24 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
 }
 
 // The flooding min-sum decoder (fpldpc_minsum_t): the same object in mode kFloodMinsum behind a handle type
-// of its own, so that staging, reference bits and the argument struct exist once.
+// of its own, so that staging, reference bits and the argument struct exist once.  fpldpc_flood_create_sat makes
+// the same handle in mode kFloodSat (the sxor fold, int16 c2v per edge).
 
 int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
                          int32_t scale_16, int32_t offset, fpldpc_minsum_t *out) {
     if (!out) return fail(FPLDPC_ERR_ARG, "null argument");
     fpldpc_layered_t lay = nullptr;
     const int st = create(code, params, 0, kFlood, post_bits, msg_bits, scale_16, offset, &lay);
+    if (st) return st;
+    *out = new fpldpc_minsum{lay};
+    return FPLDPC_OK;
+}
+
+int fpldpc_flood_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                            fpldpc_minsum_t *out) {
+    if (!out) return fail(FPLDPC_ERR_ARG, "null argument");
+    fpldpc_layered_t lay = nullptr;
+    const int st = create(code, params, 0, kFloodSxor, post_bits, msg_bits, 0, 0, &lay);
     if (st) return st;
     *out = new fpldpc_minsum{lay};
     return FPLDPC_OK;
@@ -270,6 +295,11 @@ int fpldpc_minsum_destroy(fpldpc_minsum_t dec) {
 int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
     const fpldpc_layered *d = dec->lay;
+    if (d->lc.mode == kFloodSat) {
+        snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d state=i16", d->lc.name, d->lc.grid, d->lc.threads,
+                 d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits);
+        return FPLDPC_OK;
+    }
     const int w = snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d ms=%d/16-%d state=compressed",
                            d->lc.name, d->lc.grid, d->lc.threads, d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits,
                            d->scale_16, d->offset);

@@ -48,19 +48,6 @@ constexpr size_t lay_state_bytes(int mode) { return mode == kLaySat16 ? sizeof(i
 // 32-bit words that n posteriors take in front of the control words
 __host__ __device__ constexpr size_t lay_post_words(int mode, int n) { return ((size_t)n * lay_state_bytes(mode) + 3) / 4; }
 
-// x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
-// fpldpc_flood_device.hpp: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).
-__device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
-    const int a = x < 0 ? -x : x;
-    const int b = y < 0 ? -y : y;
-    const int s = ((a + b) & mask) >> 2;
-    const int d = ((a > b ? a - b : b - a) & mask) >> 2;
-    const int p1 = max(C - s, 0);
-    const int p2 = max(C - d, 0);
-    const int r = min(a, b) + p1 - p2;
-    return ((x > 0) == (y > 0)) ? r : -r;
-}
-
 // LDS: post [n] ST (up to a whole word) | misc [kLayMisc] | (LDS_STATE) c2v [dc_max][m] ST
 //      | (table_lds) vidx [dc_max][m] uint16 | (!EXACT) cdeg [m] uint8;  ST = int16 in MODE kLaySat16, else int32
 // EXACT: every check has degree DC -- the slot loops are straight-line code (A and R: DC = 47, a

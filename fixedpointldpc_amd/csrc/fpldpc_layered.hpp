@@ -1,6 +1,6 @@
 // fpldpc_layered.hpp -- the layered (row-serial) decoder: declarations shared by fpldpc_code.cpp
 // (layer validation), fpldpc_layered.cpp (the fpldpc_layered_* and fpldpc_minsum_* C ABI), fpldpc_layered.hip,
-// fpldpc_layered_minsum.hip, fpldpc_minsum.hip, fpldpc_minsum_global.hip and fpldpc_minsum_wide.hip (kernels; through
+// fpldpc_layered_minsum.hip, fpldpc_minsum.hip, fpldpc_minsum_global.hip, fpldpc_minsum_wide.hip and fpldpc_flood_sat.hip (kernels; through
 // fpldpc_layered_device.hpp, beside which fpldpc_layered_host.hpp holds their shared choice and launch steps and
 // fpldpc_minsum_device.hpp the min-sum rule).
 //
@@ -24,8 +24,9 @@ int code_layering(const fpldpc_code &code, int layer_checks, int *L, int *layers
 // the clamps of fpldpc_layered_create_sat with int32 state (post_bits 17..24) or int16 state (<= 16), or
 // fpldpc_layered_create_minsum (int16 posteriors, 16 bytes of state per check: fpldpc_layered_minsum.hip).
 // kFloodMinsum is not a layered decoder: the flooding min-sum decoder (fpldpc_minsum_t, fpldpc_minsum.hip)
-// shares this object's host plumbing (L = m, layers = 1, no meaning).
-enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3, kFloodMinsum = 4 };
+// shares this object's host plumbing (L = m, layers = 1, no meaning), and so does kFloodSat, the saturated
+// flooding decoder with the sxor fold (fpldpc_flood_create_sat, fpldpc_flood_sat.hip: int16 c2v per edge).
+enum { kLayUnsat = 0, kLaySat32 = 1, kLaySat16 = 2, kLayMinsum = 3, kFloodMinsum = 4, kFloodSat = 5 };
 
 // Kernel choice of a layered decoder, made once at creation.
 struct LayeredChoice {
@@ -81,6 +82,10 @@ int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int 
 // The same pair for the flooding min-sum decoder (mode kFloodMinsum, fpldpc_minsum.hip): no layers.
 int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out);
 int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
+// The same pair for the saturated flooding decoder (mode kFloodSat, fpldpc_flood_sat.hip): no layers, the state in
+// LDS only (lds_state; FPLDPC_ERR_UNSUPPORTED where it does not fit).
+int flood_sat_choose(const fpldpc_code &code, int device, LayeredChoice *out);
+int flood_sat_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
 // The global form of the two min-sum decoders (fpldpc_minsum_global.hip; !lds_state), which the two pairs
 // above delegate to where the LDS form does not fit or the environment variable `env` is "global".
 // minsum_global_choose completes a choice whose mode, dc, exact and threads are set: the check state (and
@@ -119,6 +124,7 @@ struct fpldpc_layered : fpldpc::DecoderCore {
 };
 
 // Flooding min-sum decoder object (fpldpc_minsum_t): a type of its own in the C ABI over the same plumbing.
+// The saturated flooding decoder (fpldpc_flood_create_sat) is this object too.
 struct fpldpc_minsum {
-    fpldpc_layered *lay = nullptr;  // mode kFloodMinsum, owned
+    fpldpc_layered *lay = nullptr;  // mode kFloodMinsum or kFloodSat, owned
 };

@@ -1,9 +1,9 @@
 // fpldpc_layered_device.hpp -- device code the layered kernels share (fpldpc_layered.hip: the sxor fold;
 // fpldpc_layered_minsum.hip: min-sum with compressed check state; fpldpc_minsum.hip: the same rule on the
-// flooding schedule; fpldpc_minsum_global.hip: both with the state in global memory): the frame framework's
-// constants, the frame pull and the way out of the kernel, the LLR load, the syndrome and the frame
-// epilogue.  Included by those four translation units (the min-sum units through
-// fpldpc_minsum_device.hpp, the check rule they share).
+// flooding schedule; fpldpc_minsum_global.hip: both with the state in global memory; fpldpc_flood_sat.hip: the
+// sxor fold on the flooding schedule): the frame framework's constants, the frame pull and the way out of
+// the kernel, the LLR load, the box-plus, the syndrome and the frame epilogue.  Included by those translation
+// units (the min-sum units through fpldpc_minsum_device.hpp, the check rule they share).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,20 @@ constexpr size_t kLdsMax = 160 * 1024;
 constexpr int kExactDc = 47;  // the straight-line instantiation: the p = 47 array codes (A, R)
 
 __device__ __forceinline__ int lay_clamp(int x, int S) { return min(max(x, -S), S); }
+
+// x [+] y (ArrayLDPC_Decoder.cpp:677-694, sgn(0) = -1 ArrayLDPCMacro.h:222-224), as boxplus() of
+// fpldpc_flood_device.hpp: sgn(x) sgn(y) is +1 iff (x > 0) == (y > 0).  The sxor of fpldpc_layered.hip and
+// fpldpc_flood_sat.hip.
+__device__ __forceinline__ int lay_boxplus(int x, int y, int C, int mask) {
+    const int a = x < 0 ? -x : x;
+    const int b = y < 0 ? -y : y;
+    const int s = ((a + b) & mask) >> 2;
+    const int d = ((a > b ? a - b : b - a) & mask) >> 2;
+    const int p1 = max(C - s, 0);
+    const int p2 = max(C - d, 0);
+    const int r = min(a, b) + p1 - p2;
+    return ((x > 0) == (y > 0)) ? r : -r;
+}
 
 __device__ __forceinline__ int lay_load_llr(const LayeredArgs &a, size_t i) {
     return a.llr_i16 ? (int)static_cast<const int16_t *>(a.llr)[i] : static_cast<const int32_t *>(a.llr)[i];

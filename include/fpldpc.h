@@ -331,10 +331,53 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
 typedef struct fpldpc_minsum *fpldpc_minsum_t;
 int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
                          int32_t scale_16, int32_t offset, fpldpc_minsum_t *out);
+/* The saturated flooding decoder: the reference's own schedule (flooding) and check rule (the box-plus sxor in
+ * the forward/backward fold) with posteriors post_bits wide and messages msg_bits wide, defined for EVERY input
+ * (fpldpc_decode, the unsaturated int32 reference, only while its intermediates fit).
+ * S_p = 2^(post_bits-1) - 1 and S_m = 2^(msg_bits-1) - 1;  clamp(x, S) = min(max(x, -S), S);  C is the
+ * reference's Constant, int(5/8 * 2^frac_bits);  sxor and the forward/backward fold are the reference's
+ * (ArrayLDPC_Decoder.cpp:66-118, :677-694, sgn(0) = -1), in clist order.  Per frame
+ *     L[v] = clamp(LLR[v], S_p);  post[v] = L[v];  c2v[c][k] = 0
+ *     for it = 1 .. max_iter:
+ *         for every check c, all reading the same post (no order between checks):
+ *             t[k]      = clamp(post[v_k] - c2v[c][k], S_m)          (k < deg)
+ *             new       = the reference's forward/backward sxor fold of t, with C and width_mask
+ *             c2v[c][k] = new[k]
+ *         for every variable v:  post[v] = clamp(L[v] + sum of c2v[c][k] over the edges with v_k = v, S_p)
+ *         hard[v] = post[v] > 0 ? 0 : 1;  the syndrome over clist;  iters = it;  with early_term stop on a pass
+ * With params.precheck the syndrome of the clamped LLRs is tested first; on a pass the frame returns 0
+ * iterations with the channel decision and post is left untouched: the same rule as the other saturated
+ * decoders.  Outputs follow fpldpc_minsum_decode: post is int32 and totals are ADDED to.  All six fpldpc_params
+ * fields apply: frac_bits gives C and width_mask is sxor's mask.
+ * Bounds, for every input: |sxor(x, y)| <= min(|x|, |y|) + C, so every fold value and every c2v is at most
+ * S_m + C;  |post| <= S_p;  |post - c2v| <= S_p + S_m + C;  |L + sum| <= S_p + dv_max * (S_m + C) (an int32
+ * accumulator on chip; its sign is the posterior's).
+ * FPLDPC_ERR_ARG (with a message that begins "saturated flooding decoder:" and names the rule, tested before a
+ * HIP device is looked for) unless
+ *     2 <= msg_bits < post_bits <= 16   and   S_p > S_m + C.
+ * S_p > S_m + C is fpldpc_layered_create_sat's reason carried over: a posterior pinned at S_p, minus its own
+ * message, keeps its sign.  S_m + C <= 32767 follows from the rule, so the per-edge state is always int16.
+ * Identity: where no clamp acts this is fpldpc_decode at the same frac_bits and width_mask, bit for bit, in every
+ * output (the reference's stored v2c = post - c2v is t, its K1 initialisation is c2v = 0).
+ * Envelope: check degrees 2..64, n <= 65535, and the state in LDS only -- c2v [dc_max][m] int16 (up to a whole
+ * word), three int32 accumulators [n], the int16 LLRs, 16 bytes of control words and one byte per check with
+ * mixed degrees within the CU's 160 KiB; the index table joins them only where it fits and costs no resident
+ * workgroup (FPLDPC_FLOOD_SAT_TABLE=global / lds, read at creation, places it regardless: a diagnostic switch).
+ * Outside it FPLDPC_ERR_UNSUPPORTED with a message that names the decoder and the reason ("check degree above
+ * 64", or the bytes that do not fit 160 KiB of LDS); there is no global-memory form and no wide form.
+ * FPLDPC_ERR_HIP without a HIP device.
+ * The object is an fpldpc_minsum_t like any other -- the type is named after its first check rule, not after
+ * what every object of it runs: fpldpc_minsum_destroy, _set_reference, _decode, _decode_host and every
+ * fpldpc_minsum_ber_sim* entry point apply unchanged, and fpldpc_minsum_describe prints
+ * "flood_sat<DC=..,addr=computed|table|gtable,deg=exact|table> grid=N threads=N lds=N device=N
+ * sat=<post_bits>/<msg_bits> state=i16". */
+int fpldpc_flood_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                            fpldpc_minsum_t *out);
 int fpldpc_minsum_destroy(fpldpc_minsum_t dec);
 /* "flood_minsum<DC=..,addr=computed|table|gtable,deg=exact|table> grid=N threads=N lds=N device=N
  * sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed"; in the global placement
- * "flood_minsum<DC=..,addr=gtable,deg=exact|table,mem=global> ... state=compressed scratch=<bytes>". */
+ * "flood_minsum<DC=..,addr=gtable,deg=exact|table,mem=global> ... state=compressed scratch=<bytes>".
+ * A decoder of fpldpc_flood_create_sat: the line given there. */
 int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap);
 /* As fpldpc_set_reference. */
 int fpldpc_minsum_set_reference(fpldpc_minsum_t dec, const int32_t *info_index, const uint8_t *info_bits, int32_t k);

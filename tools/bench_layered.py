@@ -16,10 +16,12 @@ schedules alternate step by step inside one timed window, and the median step is
 state (fpldpc_layered_create_minsum) as a further leg; every point then ends with one line that sets its
 step time against the saturated sxor decoder's.  --flood-minsum SCALE16 OFFSET (with the two widths) adds the
 flooding min-sum decoder (fpldpc_minsum_create) to the same window, on the same frames with the same outputs
-and totals, and a line that sets it against layered min-sum when both run.  The FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
+and totals, and a line that sets it against layered min-sum when both run.  --flood-sat POST MSG adds the saturated flooding
+decoder (fpldpc_flood_create_sat: the flooding Decoder's schedule and check rule at those widths, which are its own:
+it needs no --post-bits / --msg-bits) to the same window.  The FPLDPC_LAYERED_* switches apply to the decoders this tool creates, as to any other.
 
 usage: tools/bench_layered.py [--config A W] [--steps 30] [--warmup 5] [--layer-checks 0]
-                              [--post-bits 12 --msg-bits 10 [--minsum 12 0] [--flood-minsum 12 0]]
+                              [--post-bits 12 --msg-bits 10 [--minsum 12 0] [--flood-minsum 12 0]] [--flood-sat 12 10]
 """
 import argparse
 import json
@@ -83,6 +85,8 @@ def main():
                     help="with --post-bits / --msg-bits: also time the layered min-sum decoder")
     ap.add_argument("--flood-minsum", type=int, nargs=2, metavar=("SCALE16", "OFFSET"),
                     help="with --post-bits / --msg-bits: also time the flooding min-sum decoder")
+    ap.add_argument("--flood-sat", type=int, nargs=2, metavar=("POST", "MSG"),
+                    help="also time the saturated flooding decoder at these widths")
     ap.add_argument("--git-head", default=None, help="recorded as git_head where the tree is not a git checkout")
     args = ap.parse_args()
     assert args.steps >= 20, "at least 20 timed steps"
@@ -121,6 +125,9 @@ def main():
                 legs["flood_minsum"] = Leg(torch, F.MinSumDecoder(code, max_iter=30, post_bits=args.post_bits,
                                                                   msg_bits=args.msg_bits, scale_16=args.flood_minsum[0],
                                                                   offset=args.flood_minsum[1]), code, batch, dev)
+            if args.flood_sat:
+                legs["flood_sat"] = Leg(torch, F.FloodSatDecoder(code, max_iter=30, post_bits=args.flood_sat[0],
+                                                                 msg_bits=args.flood_sat[1]), code, batch, dev)
             t_w, n_w = time.perf_counter(), 0
             while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
                 for leg in legs.values():
