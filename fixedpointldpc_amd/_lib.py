@@ -168,6 +168,9 @@ SIGNATURES = {
                                                      ctypes.POINTER(SimResult), P]),
     "fpldpc_minsum_ber_sim_source": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, I32, P, P,
                                                     ctypes.POINTER(SimResult), P]),
+    "fpldpc_float_ber_sim": (ctypes.c_int, [P, ctypes.POINTER(SimParams), ctypes.POINTER(SimResult)]),
+    "fpldpc_float_ber_sim_source": (ctypes.c_int, [P, I32, ctypes.POINTER(SimParams), I32, I32, P, P,
+                                                   ctypes.POINTER(SimResult), P]),
     "fpldpc_testing_sim_inject": (None, [I32, I64, I32, I32]),  # include/fpldpc_testing.h (tests only)
     "fpldpc_testing_harvest_compact": (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
     "fpldpc_testing_range_guard": (ctypes.c_uint32, [I32, I32, I32, ctypes.POINTER(I32)]),
@@ -412,7 +415,7 @@ class _DecoderBase:
             out["totals"] = tot
         return out
 
-    def ber_sim(self, snr, sigma, harvest=None, bias=None, source="lehmer", **kw):
+    def ber_sim(self, snr, sigma, harvest=None, bias=None, source="lehmer", float_bp=False, **kw):
         """Ordered BER/FER simulation around this decoder (fpldpc_ber_sim, fpldpc_layered_ber_sim,
         fpldpc_minsum_ber_sim): the reference harness's frame loop, batched.
         Keywords: see sim_params().  harvest = max_records or a Harvest: the failing frames and their error
@@ -420,7 +423,11 @@ class _DecoderBase:
         bias = a Bias: the simulation on the shifted channel (<family>_ber_sim_biased, with or without a
         harvest), the Bias with its weighted sums under the result's "bias" key.
         source = "lehmer" (the reference's stream, the entry points above) or "philox" (the counter-based noise
-        source, <family>_ber_sim_source, with or without a bias and a harvest); ValueError on anything else."""
+        source, <family>_ber_sim_source, with or without a bias and a harvest); ValueError on anything else.
+        float_bp = True (Decoder only, TypeError otherwise): the same simulation around the floating-point BP decode
+        of decode_float_* on the unquantised channel (fpldpc_float_ber_sim_source), every other keyword as before."""
+        if float_bp:
+            return _float_sim([self], snr, sigma, FPLDPC_COLL_HOST, source, bias, harvest, kw)[0]
         if _source(source) != FPLDPC_NOISE_LEHMER:
             return _source_sim([self], snr, sigma, FPLDPC_COLL_HOST, source, bias, harvest, kw)[0]
         if bias is not None:
@@ -1019,8 +1026,9 @@ def _biased_sim(decoders, snr, sigma, collective, bias, harvest, kw):
     return out, used.value
 
 
-def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
-    """The decoders' <family>_ber_sim_source over them on `source`; bias is None or a Bias, harvest as in _biased_sim."""
+def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw, entry=None):
+    """The decoders' <family>_ber_sim_source over them on `source`; bias is None or a Bias, harvest as in _biased_sim.
+    entry: another entry point of that signature."""
     hv = None
     if harvest is not None:
         hv = harvest if isinstance(harvest, Harvest) else Harvest(decoders[0].code, int(harvest))
@@ -1029,9 +1037,9 @@ def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
     hs = (ctypes.c_void_p * len(decoders))(*[d._h for d in decoders])
     r = SimResult()
     used = ctypes.c_int32(0)
-    _check(decoders[0]._fn("ber_sim_source")(hs, len(decoders), ctypes.byref(p), collective, _source(source),
-                                             bias._h if bias is not None else None, hv._h if hv is not None else None,
-                                             ctypes.byref(r), ctypes.byref(used)))
+    fn = entry or decoders[0]._fn("ber_sim_source")
+    _check(fn(hs, len(decoders), ctypes.byref(p), collective, _source(source), bias._h if bias is not None else None,
+              hv._h if hv is not None else None, ctypes.byref(r), ctypes.byref(used)))
     del keep
     out = {k: getattr(r, k) for k, _ in SimResult._fields_}
     if bias is not None:
@@ -1041,12 +1049,25 @@ def _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
     return out, used.value
 
 
-def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, source="lehmer", **kw):
+def _float_sim(decoders, snr, sigma, collective, source, bias, harvest, kw):
+    """fpldpc_float_ber_sim_source over Decoder objects: the float decoder belongs to fpldpc_decoder_t alone."""
+    other = sorted({type(d).__name__ for d in decoders if type(d) is not Decoder})
+    if other:
+        raise TypeError(f"float_bp=True needs Decoder objects (fpldpc_decode_float), not {', '.join(other)}")
+    return _source_sim(decoders, snr, sigma, collective, source, bias, harvest, kw, entry=lib().fpldpc_float_ber_sim_source)
+
+
+def ber_sim_multi(decoders, snr, sigma, collective=FPLDPC_COLL_AUTO, harvest=None, bias=None, source="lehmer",
+                  float_bp=False, **kw):
     """fpldpc_ber_sim_multi over several decoders (one host thread each; RCCL between distinct devices,
     host memory otherwise).  Returns the fpldpc_ber_sim result dict plus 'collective' (1 RCCL, 2 host).
     The decoders are all Decoder, all LayeredDecoder, all MinSumDecoder or all FloodSatDecoder objects (ValueError on
     a mix).
-    harvest, bias and source as in Decoder.ber_sim."""
+    harvest, bias, source and float_bp as in Decoder.ber_sim."""
+    if float_bp:
+        out, used = _float_sim(decoders, snr, sigma, collective, source, bias, harvest, kw)
+        out["collective"] = used
+        return out
     kinds = {type(d) for d in decoders}
     if len(kinds) != 1 or not kinds <= {Decoder, LayeredDecoder, MinSumDecoder, FloodSatDecoder}:
         raise ValueError("ber_sim_multi needs decoders of one class: Decoder, LayeredDecoder, MinSumDecoder or FloodSatDecoder")

@@ -42,6 +42,11 @@
 // Source (the *_ber_sim_source entry points; fpldpc_source.hip): the three places that make noise -- generate, the
 // slot's channel launch and its patch launch -- take the noise source; every other entry point passes the Lehmer
 // stream and launches and allocates what it did before.
+//
+// Float (fpldpc_float_ber_sim, fpldpc_float_ber_sim_source): the same loop around fpldpc_decode_float.  The channel --
+// host or device, either source, the patch kernel included -- writes FPLDPC_LLR_F64 into slots of 8 bytes per value, the
+// forced positions receive the double forced_llr * 2^-frac_bits (fpldpc_sim_source.hip), and there is no int16
+// overflow word to zero, copy or test.  Every other entry point issues the HIP calls it issued before.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -74,18 +79,23 @@ using namespace fpldpc;
 namespace {
 
 // The decoder behind a rank or a slot: the six things the simulation asks of one, for fpldpc_decoder_t and
-// for fpldpc_layered_t (fpldpc_minsum_t enters as the layered object it wraps).
+// for fpldpc_layered_t (fpldpc_minsum_t enters as the layered object it wraps); fl: the fpldpc_decoder_t decodes
+// with fpldpc_decode_float, from double LLRs.
 struct Dec {
     fpldpc_decoder_t flood = nullptr;
     fpldpc_layered_t lay = nullptr;
+    bool fl = false;
     DecoderCore *core() const { return flood ? static_cast<DecoderCore *>(flood) : lay; }
     explicit operator bool() const { return core() != nullptr; }
     bool operator==(const Dec &o) const { return core() == o.core(); }
     hipStream_t stream() const { return core()->stream; }
     int device() const { return core()->device; }
     fpldpc_code &code() const { return core()->code; }
-    int decode(const int16_t *llr, int32_t frames, uint32_t *hard, int32_t *iters, int32_t *bit_errors,
+    int decode(const void *llr, int32_t frames, uint32_t *hard, int32_t *iters, int32_t *bit_errors,
                hipStream_t st) const {
+        if (fl)
+            return fpldpc_decode_float(flood, static_cast<const double *>(llr), frames, hard, iters, nullptr, nullptr,
+                                       bit_errors, nullptr, st);
         return flood ? fpldpc_decode(flood, llr, FPLDPC_LLR_I16, frames, hard, iters, nullptr, nullptr, bit_errors, nullptr, st)
                      : fpldpc_layered_decode(lay, llr, FPLDPC_LLR_I16, frames, hard, iters, nullptr, nullptr, bit_errors,
                                              nullptr, st);
@@ -95,6 +105,7 @@ struct Dec {
                      : fpldpc_layered_set_reference(lay, info_index, info_bits, k);
     }
     int create_twin(Dec *out) const {
+        out->fl = fl;  // its float state is made by its first decode, as the caller's
         return flood ? decoder_create_twin(flood, &out->flood) : layered_create_twin(lay, &out->lay);
     }
     void destroy() {
@@ -106,9 +117,9 @@ struct Dec {
 };
 
 struct Slot {
-    int16_t *h_llr = nullptr;
+    void *h_llr = nullptr;     // int16 [chunk][n]; float: double
     int32_t *h_out = nullptr;  // [chunk] bit errors, [chunk] iterations, [1] int16 overflow count
-    int16_t *d_llr = nullptr;
+    void *d_llr = nullptr;
     int32_t *d_out = nullptr;
     hipEvent_t done = nullptr;
     int64_t frames = 0;
@@ -151,6 +162,10 @@ struct Rank {
     int32_t *d_bias_pos = nullptr;      // this device's copy of its positions and shifts
     double *d_bias_shift = nullptr;
     int source = FPLDPC_NOISE_LEHMER;  // the noise source of generate, launch_channel and launch_bias_patch
+    bool fl = false;                   // float: the slots hold doubles
+    int llr_type() const { return fl ? FPLDPC_LLR_F64 : FPLDPC_LLR_I16; }
+    size_t llr_size() const { return fl ? sizeof(double) : sizeof(int16_t); }
+    double forced_double() const { return std::ldexp((double)sp->forced_llr, -sp->frac_bits); }
     ~Rank() {
         // a rank that left early (an error) may still have a chunk in flight: let it finish before
         // its buffers and the twin decoder go
@@ -184,7 +199,7 @@ struct Rank {
     }
     hipStream_t exchange_stream() const { return xs ? xs : dec.stream(); }
     int setup() {  // on the decoder's device
-        const size_t llr_bytes = (size_t)chunk * n * sizeof(int16_t);
+        const size_t llr_bytes = (size_t)chunk * n * llr_size();
         s[0].dec = s[1].dec = dec;
         if (overlap) {
             int st = dec.create_twin(&twin);
@@ -300,11 +315,18 @@ struct Rank {
         x.frames = r.frames;
         if (x.frames <= 0 || sp->device_channel) return FPLDPC_OK;
         int st = fpldpc_channel_llr_src_host(source, sp->seed, x.first, (int32_t)x.frames, n, sp->snr, sp->sigma,
-                                             sp->frac_bits, sp->codeword, x.h_llr, FPLDPC_LLR_I16, sp->host_threads);
+                                             sp->frac_bits, sp->codeword, x.h_llr, llr_type(), sp->host_threads);
         if (st) return st;
-        for (int64_t f = 0; f < x.frames; f++)
-            for (int i = 0; i < sp->n_forced; i++) x.h_llr[(size_t)f * n + sp->forced_index[i]] = (int16_t)sp->forced_llr;
+        if (fl)
+            force_host(static_cast<double *>(x.h_llr), x.frames, forced_double());
+        else
+            force_host(static_cast<int16_t *>(x.h_llr), x.frames, (int16_t)sp->forced_llr);
         return FPLDPC_OK;
+    }
+    template <typename T>
+    void force_host(T *llr, int64_t frames, T value) const {
+        for (int64_t f = 0; f < frames; f++)
+            for (int i = 0; i < sp->n_forced; i++) llr[(size_t)f * n + sp->forced_index[i]] = value;
     }
     int submit(Slot &x) {
         if (x.frames <= 0) return FPLDPC_OK;
@@ -312,26 +334,29 @@ struct Rank {
         int r;
         const bool count_bits = sp->count_mode == FPLDPC_COUNT_BITS;
         if (sp->device_channel) {
-            int32_t *ovf = x.d_out + 2 * (size_t)chunk;
-            HIP_TRY(hipMemsetAsync(ovf, 0, sizeof(int32_t), st));
+            int32_t *ovf = fl ? nullptr : x.d_out + 2 * (size_t)chunk;  // float: nothing is quantised
+            if (ovf) HIP_TRY(hipMemsetAsync(ovf, 0, sizeof(int32_t), st));
             if (sp->random_info) {  // this chunk's information bits and their codewords, a codeword per frame
                 if ((r = fpldpc_info_bits(sp->info_seed, x.first, (int32_t)x.frames, k, x.d_info, st))) return r;
                 if ((r = fpldpc_encoder_encode(x.enc, x.d_info, (int32_t)x.frames, x.d_cw, st))) return r;
             }
             if ((r = launch_channel_src(source, sp->seed, x.first, (int)x.frames, n, sp->snr, sp->sigma, sp->frac_bits,
-                                        sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16,
+                                        sp->random_info ? x.d_cw : d_cw, sp->random_info ? 1 : 0, x.d_llr, llr_type(),
                                         ovf, st)))
                 return r;
             if (bias && (r = launch_bias_patch_src(source, *bias, d_bias_pos, d_bias_shift, sp->seed, x.first, (int)x.frames,
                                                    sp->snr, sp->sigma, sp->frac_bits, sp->random_info ? x.d_cw : d_cw,
-                                                   sp->random_info ? 1 : 0, x.d_llr, FPLDPC_LLR_I16, ovf, x.d_logw, st)))
+                                                   sp->random_info ? 1 : 0, x.d_llr, llr_type(), ovf, x.d_logw, st)))
                 return r;
             if (sp->n_forced > 0 &&
-                (r = launch_force_llr(x.d_llr, (int)x.frames, n, d_forced, sp->n_forced, (int16_t)sp->forced_llr, st)))
+                (r = fl ? launch_force_llr_f64(static_cast<double *>(x.d_llr), (int)x.frames, n, d_forced, sp->n_forced,
+                                               forced_double(), st)
+                        : launch_force_llr(static_cast<int16_t *>(x.d_llr), (int)x.frames, n, d_forced, sp->n_forced,
+                                           (int16_t)sp->forced_llr, st)))
                 return r;
-            HIP_TRY(hipMemcpyAsync(x.h_out + 2 * (size_t)chunk, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            if (ovf) HIP_TRY(hipMemcpyAsync(x.h_out + 2 * (size_t)chunk, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         } else {
-            HIP_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * sizeof(int16_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(x.d_llr, x.h_llr, (size_t)x.frames * n * llr_size(), hipMemcpyHostToDevice, st));
         }
         // random_info: the decoder has no reference; its hard decisions are counted against the chunk's own bits
         r = x.dec.decode(x.d_llr, (int32_t)x.frames, sp->random_info || hv ? x.d_hard : nullptr, x.d_out + chunk,
@@ -352,7 +377,7 @@ struct Rank {
     int wait(Slot &x) {
         if (x.frames <= 0) return FPLDPC_OK;
         HIP_TRY(hipEventSynchronize(x.done));
-        if (sp->device_channel && x.h_out[2 * (size_t)chunk] != 0)
+        if (sp->device_channel && !fl && x.h_out[2 * (size_t)chunk] != 0)
             return fail(FPLDPC_ERR_ARG, "LLR does not fit int16");  // as the host channel
         decoded += x.frames;
         return FPLDPC_OK;
@@ -709,6 +734,16 @@ int validate_bias(const Dec &dec, const fpldpc_sim_params *sp, const fpldpc_bias
     return FPLDPC_OK;
 }
 
+// The float decoder's envelope (float_setup, fpldpc_float.hip, which would otherwise refuse at a slot's first decode,
+// after frames have been generated) and its messages.  create_decoder bounds n and the check degree more tightly; the variable degree it does not.
+int validate_float(const Dec &dec) {
+    const fpldpc_code &c = dec.code();
+    if (c.n > 16384) return fail(FPLDPC_ERR_UNSUPPORTED, "float decoder: n > 16384");
+    if (c.dc_max > 255) return fail(FPLDPC_ERR_UNSUPPORTED, "float decoder: check degree > 255");
+    if (c.dv_max > 255) return fail(FPLDPC_ERR_UNSUPPORTED, "float decoder: variable degree > 255");
+    return FPLDPC_OK;
+}
+
 // hv: the harvest to fill; harvesting without one (a *_ber_sim_harvest call with h = NULL) is an error.
 // bias: the shift of the channel; a *_ber_sim_biased call (biasing) without one is an error
 // source: the noise source (include/fpldpc.h); the entry points without one pass the Lehmer stream
@@ -739,6 +774,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         int st = validate(dv[i], sp);
         if (st) return st;
         if (bias && (st = validate_bias(dv[i], sp, *bias))) return st;
+        if (dv[i].fl && (st = validate_float(dv[i]))) return st;
         const fpldpc_code &c = dv[i].code();
         if (hv && (hv->n != c.n || hv->m != c.m || hv->dc != c.dc_max || hv->clist != c.clist))
             return fail(FPLDPC_ERR_ARG, "the harvest was made from another code than the decoders'");
@@ -780,6 +816,7 @@ int run_sim(const std::vector<Dec> &dv, const fpldpc_sim_params *sp, int collect
         ranks[i]->hv = hv;
         ranks[i]->bias = bias;
         ranks[i]->source = source;
+        ranks[i]->fl = dv[i].fl;
         if (hipSetDevice(dv[i].device()) != hipSuccess) return fail(FPLDPC_ERR_HIP, "hipSetDevice failed");
         int st = ranks[i]->setup();
         if (st) return st;
@@ -850,6 +887,11 @@ Dec from(fpldpc_layered_t d) {
     return x;
 }
 Dec from(fpldpc_minsum_t d) { return from(d ? d->lay : nullptr); }
+Dec from_float(fpldpc_decoder_t d) {
+    Dec x = from(d);
+    x.fl = true;
+    return x;
+}
 template <typename T>
 std::vector<Dec> from(const T *decs, int32_t ndev) {
     std::vector<Dec> v;
@@ -951,6 +993,19 @@ int fpldpc_minsum_ber_sim_source(const fpldpc_minsum_t *decs, int32_t ndev, cons
                                  int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
                                  fpldpc_sim_result *out, int32_t *collective_used) {
     return run_sim(from(decs, ndev), sp, collective, out, collective_used, h, false, b, false, source);
+}
+
+int fpldpc_float_ber_sim(fpldpc_decoder_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out) {
+    if (!dec) return fail(FPLDPC_ERR_ARG, "null argument");
+    return run_sim({from_float(dec)}, sp, FPLDPC_COLL_HOST, out, nullptr);
+}
+
+int fpldpc_float_ber_sim_source(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                fpldpc_sim_result *out, int32_t *collective_used) {
+    std::vector<Dec> v;
+    for (int i = 0; decs && i < ndev; ++i) v.push_back(from_float(decs[i]));
+    return run_sim(v, sp, collective, out, collective_used, h, false, b, false, source);
 }
 
 void fpldpc_testing_sim_inject(int32_t fail_rank, int64_t fail_round, int32_t abrupt, int32_t fail_comm_init) {

@@ -1,7 +1,8 @@
 // fpldpc_sim_source.hip -- the per-frame source of a BER simulation (fpldpc_sim_params.random_info): the
 // information-bit stream, on the host and on the device, and the count of a decoded frame's information
 // bits against the bits that frame was sent with.  Between them run the encoder and the channel of
-// fpldpc_gen.hip; this unit is outside the kernel build id, as the layered and min-sum units are.
+// fpldpc_gen.hip; this unit is outside the kernel build id, as the layered and min-sum units are.  It also holds
+// the forced positions of the float simulation (fpldpc_float_ber_sim), a kernel the hashed units do not have.
 //
 // Stream: the reference's Lehmer generator (rngs.cpp:40-69, a = 48271, m = 2^31 - 1) from info_seed, apart
 // from the noise stream.  Bit i < k of frame f is the top bit of the 31-bit state after draw f*k + i, that
@@ -72,6 +73,15 @@ __global__ void __launch_bounds__(kCountThreads) count_info_kernel(const uint32_
     if (lane == 0) blkerror[f] = cnt;
 }
 
+// The float simulation's forced positions: force_llr_kernel (fpldpc_gen.hip) on a double LLR array, one thread per
+// (frame, forced position)
+__global__ void __launch_bounds__(256) force_llr_f64_kernel(double *llr, int frames, int n, const int32_t *idx, int n_idx,
+                                                            double value) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)frames * n_idx) return;
+    llr[(t / n_idx) * n + idx[t % n_idx]] = value;
+}
+
 int info_args_ok(int64_t info_seed, int64_t first_frame, int32_t frames, int32_t k, const void *out) {
     if (info_seed < 1 || info_seed > (int64_t)kMod - 1) return fail(FPLDPC_ERR_ARG, "info_seed must be in 1 .. 2^31 - 2");
     if (k < 1 || frames < 0 || first_frame < 0 || (frames > 0 && !out)) return fail(FPLDPC_ERR_ARG, "bad info_bits arguments");
@@ -93,6 +103,15 @@ int launch_count_info(const uint32_t *hard, int hard_words, const int32_t *info_
                        (hipStream_t)stream, hard, hard_words, info_idx, info, k, frames, blkerror);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FPLDPC_OK : fail_hip((int)e, "count kernel launch");
+}
+
+int launch_force_llr_f64(double *llr, int frames, int n, const int32_t *idx, int n_idx, double value, void *stream) {
+    const int64_t t = (int64_t)frames * n_idx;
+    if (t <= 0) return FPLDPC_OK;
+    hipLaunchKernelGGL(force_llr_f64_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, (hipStream_t)stream, llr,
+                       frames, n, idx, n_idx, value);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FPLDPC_OK : fail_hip((int)e, "float force kernel launch");
 }
 
 }  // namespace fpldpc

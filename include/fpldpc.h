@@ -774,6 +774,32 @@ int fpldpc_minsum_ber_sim_source(const fpldpc_minsum_t *decs, int32_t ndev, cons
                                  int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
                                  fpldpc_sim_result *out, int32_t *collective_used);
 
+/* ---------------------------------------------------------------- the simulation around the float decoder */
+/* fpldpc_ber_sim_source's loop around fpldpc_decode_float (FP_Decoder::decode_general, the reference's floating-point
+ * belief propagation) instead of fpldpc_decode: the same rounds, two chunks in flight with a twin of `dec`,
+ * FPLDPC_SIM_OVERLAP=0, the ordered stop, counter exchange, on_frame, both count_modes, several ranks with either
+ * collective, random_info, the harvest (h) and the bias (b) under their definitions and argument rules; b and h may
+ * each be NULL.  fpldpc_float_ber_sim is the second form with ndev = 1, FPLDPC_COLL_HOST, FPLDPC_NOISE_LEHMER and no
+ * bias or harvest.  Two things differ:
+ *   - the channel writes FPLDPC_LLR_F64, the unquantised double 2*snr*(...) -- host or device channel, either source,
+ *     with or without the bias's patch kernel; nothing is quantised, so there is no int16 overflow to count;
+ *   - the decode is fpldpc_decode_float with the decoder's max_iter and early_term; as there, frac_bits, width_mask
+ *     and precheck of the decoder's parameters do not apply.
+ * The fixed-point channel quantises the same double, LLR_fp = (int)(LLR * 2^frac_bits): frame f of a float run is
+ * frame f of the fixed run at the same seed, source, snr and sigma, and harvests of the two compare by frame index.
+ * Forced positions receive the double forced_llr * 2^-sp->frac_bits, the value whose quantisation at sp->frac_bits is
+ * the fixed run's forced_llr, written after the bias's patch as in the fixed run; sp->frac_bits has no other use here.
+ * FPLDPC_ERR_UNSUPPORTED with the float decoder's message, before any frame is generated, outside its envelope
+ * (n <= 16384, check and variable degrees <= 255; fpldpc_decoder_create bounds n and the check degree more
+ * tightly, not the variable degree: a decoder of a code with a variable of degree above 255 meets this refusal).
+ * A decoder stays usable both ways: a float simulation and a fixed-point one on the same
+ * object, in either order, give each call's own counters.  The twin's float state is made by its first decode, as
+ * any decoder's: its tables and its edge scratch, allocated and uploaded synchronously during round 0. */
+int fpldpc_float_ber_sim(fpldpc_decoder_t dec, const fpldpc_sim_params *sp, fpldpc_sim_result *out);
+int fpldpc_float_ber_sim_source(const fpldpc_decoder_t *decs, int32_t ndev, const fpldpc_sim_params *sp,
+                                int32_t collective, int32_t source, fpldpc_bias_t b, fpldpc_harvest_t h,
+                                fpldpc_sim_result *out, int32_t *collective_used);
+
 #ifdef __cplusplus
 }
 #endif
