@@ -41,6 +41,8 @@ SOURCES = [
     "fpldpc_minsum_wide.hip",
     # the saturated flooding decoder (sxor fold, int16 c2v per edge): on the layered plumbing, outside the build id too
     "fpldpc_flood_sat.hip",
+    # the global form of the saturated flooding decoder (codes whose state does not fit LDS): outside the build id too
+    "fpldpc_flood_sat_global.hip",
     # the per-frame source of a simulation (information bits, their count against the decode): outside the build id too
     "fpldpc_sim_source.hip",
     # the harvest of a simulation's failing frames (scan and ordered compaction): outside the build id too

@@ -97,6 +97,7 @@ SIGNATURES = {
     "fpldpc_layered_decode_host": (ctypes.c_int, [P, P, I32, I32, P, P, P, P, P, P]),
     "fpldpc_minsum_create": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, I32, ctypes.POINTER(P)]),
     "fpldpc_flood_create_sat": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, ctypes.POINTER(P)]),
+    "fpldpc_flood_create_sat_placed": (ctypes.c_int, [P, ctypes.POINTER(Params), I32, I32, I32, ctypes.POINTER(P)]),
     "fpldpc_minsum_destroy": (ctypes.c_int, [P]),
     "fpldpc_minsum_describe": (ctypes.c_int, [P, ctypes.c_char_p, SZ]),
     "fpldpc_minsum_set_reference": (ctypes.c_int, [P, P, P, I32]),
@@ -577,16 +578,23 @@ class FloodSatDecoder(_DecoderBase):
     """fpldpc_minsum_t of fpldpc_flood_create_sat: the reference's flooding schedule and sxor fold with
     posteriors post_bits wide and messages msg_bits wide (int16 c2v per edge on chip), defined for every
     input; where no clamp acts it is Decoder at the same frac_bits and width_mask bit for bit.  Check degrees
-    2..64 and the state in LDS only (FpldpcError -4 otherwise).  Same outputs and methods as MinSumDecoder,
-    whose entry points it runs through."""
+    2..64 and n <= 65535 (FpldpcError -4 otherwise).  state places the c2v and the accumulators
+    (fpldpc_flood_create_sat_placed): "lds", the default, on chip only (FpldpcError -4 where they do not fit
+    160 KiB); "global" in a scratch in global memory, for any code of the envelope (describe: "mem=global ...
+    scratch=<bytes>"); "auto" on chip wherever they fit, else global.  Every placement gives the same outputs.
+    Same outputs and methods as MinSumDecoder, whose entry points it runs through."""
 
     _ENTRY = _entries("fpldpc_minsum")
+    STATES = {"lds": 0, "global": 1, "auto": 2}  # FPLDPC_STATE_*
 
     def __init__(self, code, max_iter=30, frac_bits=4, width_mask=0xFF, early_term=True, precheck=False, device=-1,
-                 post_bits=12, msg_bits=10):
+                 post_bits=12, msg_bits=10, state="lds"):
+        if not isinstance(state, str) or state not in self.STATES:
+            raise ValueError(f"FloodSatDecoder: state must be one of 'lds', 'global', 'auto', not {state!r}")
         p = self._params(max_iter, frac_bits, width_mask, early_term, precheck, device)
         h = ctypes.c_void_p()
-        _check(lib().fpldpc_flood_create_sat(code._h, ctypes.byref(p), post_bits, msg_bits, ctypes.byref(h)))
+        _check(lib().fpldpc_flood_create_sat_placed(code._h, ctypes.byref(p), post_bits, msg_bits, self.STATES[state],
+                                                    ctypes.byref(h)))
         self._adopt(code, h, p)
 
 

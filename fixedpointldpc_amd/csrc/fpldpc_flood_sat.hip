@@ -174,19 +174,28 @@ FloodSatFn flood_sat_fn(const LayeredChoice &lc) {
 
 }  // namespace
 
-// Envelope: check degrees 2..64, n <= 65535, and the state in LDS only: the int16 c2v of every edge, three
-// int32 accumulators, the int16 LLRs, the control words and one byte per check of the degree table (unless
-// the kernel's DC is every check's degree) within the CU's 160 KiB.  The index table is placed as in the
-// layered decoders, under a switch of its own (FPLDPC_FLOOD_SAT_TABLE=global / lds places it regardless).
-int flood_sat_choose(const fpldpc_code &code, int device, LayeredChoice *out) {
+// Envelope: check degrees 2..64 and n <= 65535 in every placement.  The LDS form (FPLDPC_STATE_LDS) holds the
+// whole state on chip: the int16 c2v of every edge, three int32 accumulators, the int16 LLRs, the control words
+// and one byte per check of the degree table (unless the kernel's DC is every check's degree) within the CU's
+// 160 KiB; its index table is placed as in the layered decoders, under a switch of its own
+// (FPLDPC_FLOOD_SAT_TABLE=global / lds places it regardless).  FPLDPC_STATE_GLOBAL takes the global form
+// (fpldpc_flood_sat_global.hip) for any code of the envelope, FPLDPC_STATE_AUTO the LDS form wherever its bytes
+// fit -- the same choice as FPLDPC_STATE_LDS makes -- and the global form otherwise.
+int flood_sat_choose(const fpldpc_code &code, int device, int state, LayeredChoice *out) {
     LayeredChoice lc;
     if (int st = lay_choice_of_code(code, kFloodSat, "saturated flooding", &lc)) return st;
     if (code.n > 65535) return fail(FPLDPC_ERR_UNSUPPORTED, "saturated flooding decoder: code length above 65535");
     lc.threads = std::min(kLayMaxNT, (code.m + 63) / 64 * 64);
     const size_t base = fs_table_offset(code.n, code.dc_max, code.m) + (lc.exact ? 0 : (size_t)code.m);
+    if (state == FPLDPC_STATE_GLOBAL || (state == FPLDPC_STATE_AUTO && base > kLdsMax)) {
+        if (int st = flood_sat_global_choose(code, device, &lc)) return st;
+        *out = lc;
+        return FPLDPC_OK;
+    }
     if (base > kLdsMax)
         return fail(FPLDPC_ERR_UNSUPPORTED, "saturated flooding decoder: " + std::to_string(base) +
-                                                " bytes of state (int16 c2v per edge, three int32 accumulators, the LLRs) do not fit 160 KiB of LDS");
+                                                " bytes of state (int16 c2v per edge, three int32 accumulators, the LLRs) do not fit 160 KiB of LDS"
+                                                " (FPLDPC_STATE_GLOBAL or FPLDPC_STATE_AUTO of fpldpc_flood_create_sat_placed keeps them in global memory)");
     if (int st = lay_choose_lds(flood_sat_fn(lc), code, base, "FPLDPC_FLOOD_SAT_TABLE", device, "saturated flooding", "flood_sat", &lc))
         return st;
     *out = lc;
@@ -194,6 +203,7 @@ int flood_sat_choose(const fpldpc_code &code, int device, LayeredChoice *out) {
 }
 
 int flood_sat_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream) {
+    if (!lc.lds_state) return flood_sat_global_launch(lc, args, stream);
     return lay_launch(flood_sat_fn(lc), lc, args, args, stream, "saturated flooding");
 }
 

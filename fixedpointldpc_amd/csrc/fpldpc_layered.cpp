@@ -50,11 +50,12 @@ int upload(fpldpc_layered *d) {
 // The three creation entry points (the arguments of the saturated and the min-sum decoder are validated
 // before anything touches HIP).
 // kFlood: the flooding min-sum decoder (fpldpc_minsum_create) over the same object; layer_checks unused.
-// kFloodSxor: the saturated flooding decoder (fpldpc_flood_create_sat), likewise; scale_16 and offset unused.
+// kFloodSxor: the saturated flooding decoder (fpldpc_flood_create_sat_placed), likewise; scale_16 and offset unused,
+// `state` is its state placement (FPLDPC_STATE_*; unused by the other kinds).
 enum Kind { kUnsat, kSat, kMinsum, kFlood, kFloodSxor };
 
 int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks, Kind kind, int32_t post_bits,
-           int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out) {
+           int32_t msg_bits, int32_t scale_16, int32_t offset, fpldpc_layered_t *out, int32_t state = FPLDPC_STATE_LDS) {
     const bool sat = kind == kSat;
     if (!code || !out) return fail(FPLDPC_ERR_ARG, "null argument");
     fpldpc_params p;
@@ -89,6 +90,9 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
         if (sat_limit(post_bits) <= sat_limit(msg_bits) + constant_c(p.frac_bits))
             return fail(FPLDPC_ERR_ARG, "saturated flooding decoder: need S_p > S_m + C (2^(post_bits-1) - 1 > 2^(msg_bits-1) - 1 + " +
                                             std::to_string(constant_c(p.frac_bits)) + ")");
+        if (state != FPLDPC_STATE_LDS && state != FPLDPC_STATE_GLOBAL && state != FPLDPC_STATE_AUTO)
+            return fail(FPLDPC_ERR_ARG, "saturated flooding decoder: state " + std::to_string(state) +
+                                            " is none of FPLDPC_STATE_LDS (0), FPLDPC_STATE_GLOBAL (1), FPLDPC_STATE_AUTO (2)");
         mode = kFloodSat;
     }
     const bool flooding = kind == kFlood || kind == kFloodSxor;
@@ -114,7 +118,7 @@ int create(fpldpc_code_t code, const fpldpc_params *params, int32_t layer_checks
         d->offset = offset;
     }
     st = kind == kFlood       ? flood_minsum_choose(d->code, dev, &d->lc)
-         : kind == kFloodSxor ? flood_sat_choose(d->code, dev, &d->lc)
+         : kind == kFloodSxor ? flood_sat_choose(d->code, dev, state, &d->lc)
          : kind == kMinsum    ? layered_minsum_choose(d->code, L, dev, &d->lc)
                               : layered_choose(d->code, L, dev, mode, &d->lc);
     if (st) return st;
@@ -262,8 +266,9 @@ int fpldpc_layered_decode_host(fpldpc_layered_t dec, const void *llr, int32_t ll
 }
 
 // The flooding min-sum decoder (fpldpc_minsum_t): the same object in mode kFloodMinsum behind a handle type
-// of its own, so that staging, reference bits and the argument struct exist once.  fpldpc_flood_create_sat makes
-// the same handle in mode kFloodSat (the sxor fold, int16 c2v per edge).
+// of its own, so that staging, reference bits and the argument struct exist once.  fpldpc_flood_create_sat_placed
+// (and fpldpc_flood_create_sat, its FPLDPC_STATE_LDS) makes the same handle in mode kFloodSat (the sxor fold, int16
+// c2v per edge).
 
 int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
                          int32_t scale_16, int32_t offset, fpldpc_minsum_t *out) {
@@ -275,14 +280,19 @@ int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_
     return FPLDPC_OK;
 }
 
-int fpldpc_flood_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
-                            fpldpc_minsum_t *out) {
+int fpldpc_flood_create_sat_placed(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                                   int32_t state, fpldpc_minsum_t *out) {
     if (!out) return fail(FPLDPC_ERR_ARG, "null argument");
     fpldpc_layered_t lay = nullptr;
-    const int st = create(code, params, 0, kFloodSxor, post_bits, msg_bits, 0, 0, &lay);
+    const int st = create(code, params, 0, kFloodSxor, post_bits, msg_bits, 0, 0, &lay, state);
     if (st) return st;
     *out = new fpldpc_minsum{lay};
     return FPLDPC_OK;
+}
+
+int fpldpc_flood_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
+                            fpldpc_minsum_t *out) {
+    return fpldpc_flood_create_sat_placed(code, params, post_bits, msg_bits, FPLDPC_STATE_LDS, out);
 }
 
 int fpldpc_minsum_destroy(fpldpc_minsum_t dec) {
@@ -296,8 +306,10 @@ int fpldpc_minsum_describe(fpldpc_minsum_t dec, char *buf, size_t cap) {
     if (!dec || !buf || cap == 0) return fail(FPLDPC_ERR_ARG, "null argument");
     const fpldpc_layered *d = dec->lay;
     if (d->lc.mode == kFloodSat) {
-        snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d state=i16", d->lc.name, d->lc.grid, d->lc.threads,
-                 d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits);
+        const int w = snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d state=i16", d->lc.name, d->lc.grid,
+                               d->lc.threads, d->lc.lds_bytes, d->device, d->post_bits, d->msg_bits);
+        // the global form: the bytes of its scratch
+        if (!d->lc.lds_state && w > 0 && (size_t)w < cap) snprintf(buf + w, cap - w, " scratch=%zu", d->lc.scratch_bytes);
         return FPLDPC_OK;
     }
     const int w = snprintf(buf, cap, "%s grid=%d threads=%d lds=%zu device=%d sat=%d/%d ms=%d/16-%d state=compressed",

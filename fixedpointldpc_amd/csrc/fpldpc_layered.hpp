@@ -82,10 +82,18 @@ int layered_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int 
 // The same pair for the flooding min-sum decoder (mode kFloodMinsum, fpldpc_minsum.hip): no layers.
 int flood_minsum_choose(const fpldpc_code &code, int device, LayeredChoice *out);
 int flood_minsum_launch(const LayeredChoice &lc, const LayeredArgs &args, int scale_16, int offset, void *stream);
-// The same pair for the saturated flooding decoder (mode kFloodSat, fpldpc_flood_sat.hip): no layers, the state in
-// LDS only (lds_state; FPLDPC_ERR_UNSUPPORTED where it does not fit).
-int flood_sat_choose(const fpldpc_code &code, int device, LayeredChoice *out);
+// The same pair for the saturated flooding decoder (mode kFloodSat, fpldpc_flood_sat.hip): no layers.  `state` is
+// fpldpc_flood_create_sat_placed's (validated by the caller): FPLDPC_STATE_LDS keeps the state in LDS only
+// (lds_state; FPLDPC_ERR_UNSUPPORTED where it does not fit), _GLOBAL takes the global form, _AUTO the LDS form
+// wherever it fits and the global form otherwise.
+int flood_sat_choose(const fpldpc_code &code, int device, int state, LayeredChoice *out);
 int flood_sat_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
+// The global form of the saturated flooding decoder (fpldpc_flood_sat_global.hip; !lds_state), which the pair
+// above delegates to.  flood_sat_global_choose completes a choice whose mode, dc, exact and threads are set: the
+// int16 c2v of every edge and the three accumulators in scratch_bytes = grid * slice of global memory, passed
+// as c2v_scratch.
+int flood_sat_global_choose(const fpldpc_code &code, int device, LayeredChoice *lc);
+int flood_sat_global_launch(const LayeredChoice &lc, const LayeredArgs &args, void *stream);
 // The global form of the two min-sum decoders (fpldpc_minsum_global.hip; !lds_state), which the two pairs
 // above delegate to where the LDS form does not fit or the environment variable `env` is "global".
 // minsum_global_choose completes a choice whose mode, dc, exact and threads are set: the check state (and

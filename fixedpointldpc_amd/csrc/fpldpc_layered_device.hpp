@@ -1,7 +1,8 @@
 // fpldpc_layered_device.hpp -- device code the layered kernels share (fpldpc_layered.hip: the sxor fold;
 // fpldpc_layered_minsum.hip: min-sum with compressed check state; fpldpc_minsum.hip: the same rule on the
 // flooding schedule; fpldpc_minsum_global.hip: both with the state in global memory; fpldpc_flood_sat.hip: the
-// sxor fold on the flooding schedule): the frame framework's constants, the frame pull and the way out of
+// sxor fold on the flooding schedule; fpldpc_flood_sat_global.hip: the same with the state in global memory):
+// the frame framework's constants, the frame pull and the way out of
 // the kernel, the LLR load, the box-plus, the syndrome and the frame epilogue.  Included by those translation
 // units (the min-sum units through fpldpc_minsum_device.hpp, the check rule they share).
 #pragma once

@@ -1,5 +1,5 @@
 // fpldpc_layered_host.hpp -- host code the layered units share (fpldpc_layered.hip, fpldpc_layered_minsum.hip,
-// fpldpc_minsum.hip, fpldpc_minsum_global.hip, fpldpc_flood_sat.hip): the steps of a kernel choice (degree bucket, residency probe,
+// fpldpc_minsum.hip, fpldpc_minsum_global.hip, fpldpc_flood_sat.hip, fpldpc_flood_sat_global.hip): the steps of a kernel choice (degree bucket, residency probe,
 // index-table placement, grid) and the launch.  Templates over the kernel's function pointer: the kernels are
 // templates in each unit's anonymous namespace.  `who` is the decoder's name in the error texts ("layered",
 // "layered min-sum", "flooding min-sum", "saturated flooding").  Included by those translation units only, after

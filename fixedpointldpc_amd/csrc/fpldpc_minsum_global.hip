@@ -20,45 +20,18 @@
 // kept from an earlier read of the same buffer.  Plain stores (the refill with L, the final clamp) are
 // complete at the barrier that follows them.
 #include "fpldpc_layered_host.hpp"
+#include "fpldpc_global_state.hpp"
 #include "fpldpc_minsum_device.hpp"
 
 namespace fpldpc {
 namespace {
 
-// LDS: vec [n] int16 (up to a whole word) | misc [kLayMisc] | (!EXACT, where it fits) cdeg [m] uint8
-__host__ __device__ constexpr size_t mg_misc_word(int n) { return ((size_t)n * sizeof(int16_t) + 3) / 4; }
-__host__ __device__ constexpr size_t mg_base_bytes(int n) { return (mg_misc_word(n) + kLayMisc) * sizeof(int); }
-__host__ __device__ constexpr bool mg_deg_in_lds(int n, int m) { return mg_base_bytes(n) + (size_t)m <= kLdsMax; }
-
-__host__ __device__ constexpr size_t mg_round_slice(size_t bytes) { return (bytes + 255) / 256 * 256; }
+// The LDS layout, mg_round_slice, mg_degrees, fg_load and FgAcc: fpldpc_global_state.hpp.
 // a workgroup's slice of the scratch.  Flooding: state [m] uint4 | acc [3][n] int32; layered: state [m] uint4
 __host__ __device__ constexpr size_t fg_slice_bytes(int n, int m) {
     return mg_round_slice(kMsStateBytes * (size_t)m + 3 * sizeof(int) * (size_t)n);
 }
 __host__ __device__ constexpr size_t lg_slice_bytes(int m) { return mg_round_slice(kMsStateBytes * (size_t)m); }
-
-// The degree table of a predicated kernel: staged behind the control words where it fits, else a.cdeg.
-// (The first frame pull's barriers come between the staging and the first read.)
-template <bool EXACT>
-__device__ __forceinline__ const uint8_t *mg_degrees(const LayeredArgs &a, int *smem) {
-    if constexpr (EXACT) {
-        return nullptr;
-    } else {
-        if (!mg_deg_in_lds(a.n, a.m)) return a.cdeg;
-        uint8_t *const ld = reinterpret_cast<uint8_t *>(smem) + mg_base_bytes(a.n);
-        for (int i = threadIdx.x; i < a.m; i += blockDim.x) ld[i] = a.cdeg[i];
-        return ld;
-    }
-}
-
-__device__ __forceinline__ int fg_load(const int *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// An accumulator word as lay_syndrome reads it (post[v] <= 0), through fg_load.
-struct FgAcc {
-    int raw;
-    __device__ __forceinline__ bool operator<=(int x) const { return fg_load(&raw) <= x; }
-};
 
 // flood_minsum with its check state and accumulators in the workgroup's slice.  DC / EXACT as there.
 template <int DC, bool EXACT>

@@ -359,12 +359,13 @@ int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_
  * message, keeps its sign.  S_m + C <= 32767 follows from the rule, so the per-edge state is always int16.
  * Identity: where no clamp acts this is fpldpc_decode at the same frac_bits and width_mask, bit for bit, in every
  * output (the reference's stored v2c = post - c2v is t, its K1 initialisation is c2v = 0).
- * Envelope: check degrees 2..64, n <= 65535, and the state in LDS only -- c2v [dc_max][m] int16 (up to a whole
- * word), three int32 accumulators [n], the int16 LLRs, 16 bytes of control words and one byte per check with
- * mixed degrees within the CU's 160 KiB; the index table joins them only where it fits and costs no resident
+ * Envelope: check degrees 2..64, n <= 65535, and, in this call, the state in LDS -- c2v [dc_max][m] int16 (up to
+ * a whole word), three int32 accumulators [n], the int16 LLRs, 16 bytes of control words and one byte per check
+ * with mixed degrees within the CU's 160 KiB; the index table joins them only where it fits and costs no resident
  * workgroup (FPLDPC_FLOOD_SAT_TABLE=global / lds, read at creation, places it regardless: a diagnostic switch).
  * Outside it FPLDPC_ERR_UNSUPPORTED with a message that names the decoder and the reason ("check degree above
- * 64", or the bytes that do not fit 160 KiB of LDS); there is no global-memory form and no wide form.
+ * 64", or the bytes that do not fit 160 KiB of LDS).  A code whose state does not fit is decoded by the global
+ * form, which fpldpc_flood_create_sat_placed (below) gives on request; there is no wide form.
  * FPLDPC_ERR_HIP without a HIP device.
  * The object is an fpldpc_minsum_t like any other -- the type is named after its first check rule, not after
  * what every object of it runs: fpldpc_minsum_destroy, _set_reference, _decode, _decode_host and every
@@ -373,6 +374,27 @@ int fpldpc_minsum_create(fpldpc_code_t code, const fpldpc_params *params, int32_
  * sat=<post_bits>/<msg_bits> state=i16". */
 int fpldpc_flood_create_sat(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits, int32_t msg_bits,
                             fpldpc_minsum_t *out);
+/* The same decoder -- definition, rules on the widths, outputs and entry points as fpldpc_flood_create_sat -- with
+ * the placement of its state chosen by the caller:
+ *     FPLDPC_STATE_LDS     fpldpc_flood_create_sat itself, its refusal and message included;
+ *     FPLDPC_STATE_GLOBAL  the global form for any code of the envelope (check degrees 2..64, n <= 65535), also one
+ *                          whose state fits LDS: LDS keeps the int16 LLRs, 16 bytes of control words and the degree
+ *                          table (where 2 n + 16 + m bytes fit 160 KiB); every resident workgroup owns a slice of a
+ *                          scratch the decoder allocates at creation, c2v [dc_max][m] int16 (up to a whole word) and
+ *                          three int32 accumulators [n], rounded up to 256 bytes; the index table stays in global
+ *                          memory and a forward array code reads it too;
+ *     FPLDPC_STATE_AUTO    the LDS form wherever its bytes fit (kernel, grid and describe line as FPLDPC_STATE_LDS
+ *                          gives them), else the global form.
+ * Every placement gives the same outputs, bit for bit.  Any other `state` is FPLDPC_ERR_ARG with a message that
+ * begins "saturated flooding decoder:", tested with the widths before a HIP device is looked for.
+ * fpldpc_minsum_describe prints the global form as
+ * "flood_sat<DC=..,addr=gtable,deg=exact|table,mem=global> grid=N threads=N lds=N device=N
+ * sat=<post_bits>/<msg_bits> state=i16 scratch=<bytes>" (scratch = grid * slice). */
+#define FPLDPC_STATE_LDS 0
+#define FPLDPC_STATE_GLOBAL 1
+#define FPLDPC_STATE_AUTO 2
+int fpldpc_flood_create_sat_placed(fpldpc_code_t code, const fpldpc_params *params, int32_t post_bits,
+                                   int32_t msg_bits, int32_t state, fpldpc_minsum_t *out);
 int fpldpc_minsum_destroy(fpldpc_minsum_t dec);
 /* "flood_minsum<DC=..,addr=computed|table|gtable,deg=exact|table> grid=N threads=N lds=N device=N
  * sat=<post_bits>/<msg_bits> ms=<scale_16>/16-<offset> state=compressed"; in the global placement
