@@ -36,6 +36,7 @@
 #include <memory>
 
 #include "fpldpc_bias.hpp"
+#include "fpldpc_internal.hpp"
 
 namespace fpldpc {
 namespace {
@@ -162,33 +163,43 @@ int bias_upload_tables(const fpldpc_bias &b, int32_t **d_pos, double **d_shift) 
     return FPLDPC_OK;
 }
 
-int launch_bias_patch(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, int64_t seed, int64_t first_frame,
-                      int frames, double snr, double sigma, int frac_bits, const uint8_t *cw, int cw_per_frame, void *out,
-                      int out_type, int *overflow, double *logw, void *stream) {
-    if (frames <= 0 || (b.count() == 0 && !logw)) return FPLDPC_OK;
+int bias_bind(fpldpc_bias *b) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    if (b->device >= 0 && b->device != dev) return fail(FPLDPC_ERR_ARG, "bias already bound to another device");
+    if (b->device < 0) {
+        if (const int st = bias_upload_tables(*b, &b->d_pos, &b->d_shift)) return st;
+        b->device = dev;
+    }
+    return FPLDPC_OK;
+}
+
+int launch_bias_patch(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, const ChannelArgs &c, void *stream) {
+    if (c.frames <= 0 || (b.count() == 0 && !c.logw)) return FPLDPC_OK;
     BiasArgs a;
     uint64_t x = kMul;
     for (int j = 0; j < kPowBits; ++j) {
         a.apow[j] = x;
         x = (uint64_t)(((unsigned __int128)x * x) % kMod);
     }
-    a.seed = (uint64_t)seed;
-    a.first_frame = first_frame;
-    a.frames = frames;
+    a.seed = (uint64_t)c.seed;
+    a.first_frame = c.first_frame;
+    a.frames = c.frames;
     a.n = b.n;
-    a.frac = frac_bits;
-    a.out_type = out_type;
-    a.cw_per_frame = cw_per_frame;
+    a.frac = c.frac_bits;
+    a.out_type = c.out_type;
+    a.cw_per_frame = c.cw_per_frame;
     a.count = b.count();
-    a.snr = snr;
-    a.sigma = sigma;
-    a.cw = cw;
+    a.snr = c.snr;
+    a.sigma = c.sigma;
+    a.cw = c.cw;
     a.pos = d_pos;
     a.shift = d_shift;
-    a.out = out;
-    a.overflow = overflow;
-    a.logw = logw;
-    hipLaunchKernelGGL(bias_patch_kernel, dim3((unsigned)((frames + kPer - 1) / kPer)), dim3(kThreads), 0, (hipStream_t)stream,
+    a.out = c.out;
+    a.overflow = c.overflow;
+    a.logw = c.logw;
+    hipLaunchKernelGGL(bias_patch_kernel, dim3((unsigned)((c.frames + kPer - 1) / kPer)), dim3(kThreads), 0, (hipStream_t)stream,
                        a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FPLDPC_OK : hip_fail(e, "bias patch kernel launch");
@@ -244,19 +255,12 @@ int fpldpc_bias_channel_llr(fpldpc_bias_t b, int64_t seed, int64_t first_frame, 
                             int32_t *overflow, double *logw, void *stream) {
     if (const int st = channel_rules(b, seed, first_frame, frames, frac_bits, out, out_type, cw_per_frame)) return st;
     if (frames == 0) return FPLDPC_OK;
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    if (b->device >= 0 && b->device != dev) return fail(FPLDPC_ERR_ARG, "bias already bound to another device");
-    if (b->device < 0) {
-        if (const int st = bias_upload_tables(*b, &b->d_pos, &b->d_shift)) return st;
-        b->device = dev;
-    }
+    if (const int st = bias_bind(b)) return st;
     if (const int st = launch_channel(seed, first_frame, frames, b->n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type,
                                       overflow, stream))
         return st;
-    return launch_bias_patch(*b, b->d_pos, b->d_shift, seed, first_frame, frames, snr, sigma, frac_bits, cw, cw_per_frame, out,
-                             out_type, overflow, logw, stream);
+    const ChannelArgs a{seed, first_frame, frames, b->n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow, logw};
+    return launch_bias_patch(*b, b->d_pos, b->d_shift, a, stream);
 }
 
 }  // extern "C"

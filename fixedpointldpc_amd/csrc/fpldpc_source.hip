@@ -146,42 +146,31 @@ __global__ void __launch_bounds__(kPatchThreads) philox_patch_kernel(PhiloxArgs 
 
 int hip_fail(hipError_t e, const char *what) { return fail_hip((int)e, what); }
 
-PhiloxArgs args(int64_t seed, int64_t first_frame, int frames, int n, double snr, double sigma, int frac_bits,
-                const uint8_t *cw, int cw_per_frame, void *out, int out_type, int *overflow) {
+PhiloxArgs args(const ChannelArgs &c, int n) {
     PhiloxArgs a{};
-    a.seed = (uint64_t)seed;
-    a.first_frame = first_frame;
-    a.frames = frames;
+    a.seed = (uint64_t)c.seed;
+    a.first_frame = c.first_frame;
+    a.frames = c.frames;
     a.n = n;
-    a.frac = frac_bits;
-    a.out_type = out_type;
-    a.cw_per_frame = cw_per_frame;
-    a.snr = snr;
-    a.sigma = sigma;
-    a.cw = cw;
-    a.out = out;
-    a.overflow = overflow;
+    a.frac = c.frac_bits;
+    a.out_type = c.out_type;
+    a.cw_per_frame = c.cw_per_frame;
+    a.snr = c.snr;
+    a.sigma = c.sigma;
+    a.cw = c.cw;
+    a.out = c.out;
+    a.overflow = c.overflow;
     return a;
 }
 
-// the argument rules of a channel call on the Philox source
-int philox_rules(int64_t seed, int64_t first_frame, int32_t frames, int32_t n, int32_t frac_bits, const void *out,
-                 int32_t out_type, int32_t cw_per_frame) {
-    if (!out || n <= 0 || frac_bits < 0 || frac_bits > 24 || !philox_range_ok(seed, first_frame, frames))
-        return fail(FPLDPC_ERR_ARG, "bad channel arguments (philox: 0 <= seed, first_frame + frames < 2^63)");
-    if (out_type != FPLDPC_LLR_I32 && out_type != FPLDPC_LLR_I16 && out_type != FPLDPC_LLR_F64)
-        return fail(FPLDPC_ERR_ARG, "bad out_type");
-    if (cw_per_frame != 0 && cw_per_frame != 1) return fail(FPLDPC_ERR_ARG, "cw_per_frame must be 0 or 1");
-    return FPLDPC_OK;
-}
+int bad_source() { return fail(FPLDPC_ERR_ARG, "bad noise source (FPLDPC_NOISE_LEHMER or FPLDPC_NOISE_PHILOX)"); }
 
 }  // namespace
 
-int launch_channel_philox(int64_t seed, int64_t first_frame, int frames, int n, double snr, double sigma, int frac_bits,
-                          const uint8_t *cw, int cw_per_frame, void *out, int out_type, int *overflow, void *stream) {
-    if (frames <= 0) return FPLDPC_OK;
-    const PhiloxArgs a = args(seed, first_frame, frames, n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow);
-    const uint64_t threads = (uint64_t)frames * (((uint64_t)n + 1) / 2);
+int launch_channel_philox(const ChannelArgs &c, void *stream) {
+    if (c.frames <= 0) return FPLDPC_OK;
+    const PhiloxArgs a = args(c, c.n);
+    const uint64_t threads = (uint64_t)c.frames * (((uint64_t)c.n + 1) / 2);
     const uint64_t blocks = (threads + kChanThreads - 1) / kChanThreads;
     if (blocks > 0x7fffffffull) return fail(FPLDPC_ERR_ARG, "channel: too many values for one call (frames * n)");
     hipLaunchKernelGGL(philox_channel_kernel, dim3((unsigned)blocks), dim3(kChanThreads), 0, (hipStream_t)stream, a);
@@ -189,16 +178,15 @@ int launch_channel_philox(int64_t seed, int64_t first_frame, int frames, int n, 
     return e == hipSuccess ? FPLDPC_OK : hip_fail(e, "philox channel kernel launch");
 }
 
-int launch_bias_patch_philox(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, int64_t seed,
-                             int64_t first_frame, int frames, double snr, double sigma, int frac_bits, const uint8_t *cw,
-                             int cw_per_frame, void *out, int out_type, int *overflow, double *logw, void *stream) {
-    if (frames <= 0 || (b.count() == 0 && !logw)) return FPLDPC_OK;
-    PhiloxArgs a = args(seed, first_frame, frames, b.n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow);
+int launch_bias_patch_philox(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, const ChannelArgs &c,
+                             void *stream) {
+    if (c.frames <= 0 || (b.count() == 0 && !c.logw)) return FPLDPC_OK;
+    PhiloxArgs a = args(c, b.n);
     a.count = b.count();
     a.pos = d_pos;
     a.shift = d_shift;
-    a.logw = logw;
-    hipLaunchKernelGGL(philox_patch_kernel, dim3((unsigned)((frames + kPer - 1) / kPer)), dim3(kPatchThreads), 0,
+    a.logw = c.logw;
+    hipLaunchKernelGGL(philox_patch_kernel, dim3((unsigned)((c.frames + kPer - 1) / kPer)), dim3(kPatchThreads), 0,
                        (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FPLDPC_OK : hip_fail(e, "philox patch kernel launch");
@@ -216,10 +204,10 @@ int fpldpc_channel_llr_src(int32_t source, int64_t seed, int64_t first_frame, in
     if (source == FPLDPC_NOISE_LEHMER)
         return fpldpc_channel_llr(seed, first_frame, frames, n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type,
                                   overflow, stream);
-    if (source != FPLDPC_NOISE_PHILOX) return fail(FPLDPC_ERR_ARG, "bad noise source (FPLDPC_NOISE_LEHMER or FPLDPC_NOISE_PHILOX)");
-    if (const int st = philox_rules(seed, first_frame, frames, n, frac_bits, out, out_type, cw_per_frame)) return st;
-    return launch_channel_philox(seed, first_frame, frames, n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow,
-                                 stream);
+    if (source != FPLDPC_NOISE_PHILOX) return bad_source();
+    const ChannelArgs a{seed, first_frame, frames, n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow};
+    if (const int st = philox_rules(a)) return st;
+    return launch_channel_philox(a, stream);
 }
 
 int fpldpc_bias_channel_llr_src(fpldpc_bias_t b, int32_t source, int64_t seed, int64_t first_frame, int32_t frames,
@@ -228,23 +216,14 @@ int fpldpc_bias_channel_llr_src(fpldpc_bias_t b, int32_t source, int64_t seed, i
     if (source == FPLDPC_NOISE_LEHMER)
         return fpldpc_bias_channel_llr(b, seed, first_frame, frames, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type,
                                        overflow, logw, stream);
-    if (source != FPLDPC_NOISE_PHILOX) return fail(FPLDPC_ERR_ARG, "bad noise source (FPLDPC_NOISE_LEHMER or FPLDPC_NOISE_PHILOX)");
+    if (source != FPLDPC_NOISE_PHILOX) return bad_source();
     if (!b) return fail(FPLDPC_ERR_ARG, "bias: null bias");
-    if (const int st = philox_rules(seed, first_frame, frames, b->n, frac_bits, out, out_type, cw_per_frame)) return st;
+    const ChannelArgs a{seed, first_frame, frames, b->n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow, logw};
+    if (const int st = philox_rules(a)) return st;
     if (frames == 0) return FPLDPC_OK;
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    if (b->device >= 0 && b->device != dev) return fail(FPLDPC_ERR_ARG, "bias already bound to another device");
-    if (b->device < 0) {
-        if (const int st = bias_upload_tables(*b, &b->d_pos, &b->d_shift)) return st;
-        b->device = dev;
-    }
-    if (const int st = launch_channel_philox(seed, first_frame, frames, b->n, snr, sigma, frac_bits, cw, cw_per_frame, out,
-                                             out_type, overflow, stream))
-        return st;
-    return launch_bias_patch_philox(*b, b->d_pos, b->d_shift, seed, first_frame, frames, snr, sigma, frac_bits, cw, cw_per_frame,
-                                    out, out_type, overflow, logw, stream);
+    if (const int st = bias_bind(b)) return st;
+    if (const int st = launch_channel_philox(a, stream)) return st;
+    return launch_bias_patch_philox(*b, b->d_pos, b->d_shift, a, stream);
 }
 
 }  // extern "C"

@@ -1,11 +1,12 @@
 // fpldpc_source.hpp -- the counter-based noise source (include/fpldpc.h, FPLDPC_NOISE_PHILOX): Philox4x32-10
 // and the two 53-bit uniforms of a pair, for the host twins (fpldpc_channel.cpp) and the device kernels
-// (fpldpc_source.hip), and what fpldpc_sim.cpp takes from fpldpc_source.hip: the two launchers that stand beside
-// launch_channel and launch_bias_patch.
+// (fpldpc_source.hip), their shared argument rules, and what the simulation (fpldpc_sim_rank.hpp) takes from
+// fpldpc_source.hip: the two launchers that stand beside launch_channel and launch_bias_patch.
 #pragma once
 #include <cstdint>
 
 #include "fpldpc_bias.hpp"
+#include "fpldpc_channel_args.hpp"
 #include "fpldpc_internal.hpp"
 
 #if defined(__HIP__)
@@ -48,33 +49,33 @@ FPLDPC_HD void philox_uniforms(uint64_t seed, uint64_t frame, uint32_t pair, dou
     *u2 = (double)b * 0x1p-53;
 }
 
-// What FPLDPC_NOISE_PHILOX asks of seed and frame range: 0 <= seed, 0 <= first_frame, first_frame + frames < 2^63
-// (the Lehmer stream's rules stay with its own entry points).
-inline bool philox_range_ok(int64_t seed, int64_t first_frame, int32_t frames) {
-    return seed >= 0 && first_frame >= 0 && frames >= 0 && first_frame <= INT64_MAX - (int64_t)frames;
+// The argument rules of a channel call on the Philox source, for the host twins and the device entry points alike:
+// the channel's own, with 0 <= seed, 0 <= first_frame and first_frame + frames < 2^63 in place of the Lehmer stream's.
+inline int philox_rules(const ChannelArgs &a) {
+    if (!a.out || a.n <= 0 || a.frac_bits < 0 || a.frac_bits > 24 || a.seed < 0 || a.first_frame < 0 || a.frames < 0 ||
+        a.first_frame > INT64_MAX - (int64_t)a.frames)
+        return fail(FPLDPC_ERR_ARG, "bad channel arguments (philox: 0 <= seed, first_frame + frames < 2^63)");
+    if (a.out_type != FPLDPC_LLR_I32 && a.out_type != FPLDPC_LLR_I16 && a.out_type != FPLDPC_LLR_F64)
+        return fail(FPLDPC_ERR_ARG, "bad out_type");
+    if (a.cw_per_frame != 0 && a.cw_per_frame != 1) return fail(FPLDPC_ERR_ARG, "cw_per_frame must be 0 or 1");
+    return FPLDPC_OK;
 }
 
-// The Philox channel over `frames` frames, launch_channel's arguments.
-int launch_channel_philox(int64_t seed, int64_t first_frame, int frames, int n, double snr, double sigma, int frac_bits,
-                          const uint8_t *cw, int cw_per_frame, void *out, int out_type, int *overflow, void *stream);
-// The patch kernel behind it, launch_bias_patch's arguments.
-int launch_bias_patch_philox(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, int64_t seed,
-                             int64_t first_frame, int frames, double snr, double sigma, int frac_bits, const uint8_t *cw,
-                             int cw_per_frame, void *out, int out_type, int *overflow, double *logw, void *stream);
+// The Philox channel over a.frames frames, as launch_channel (a.logw unused).
+int launch_channel_philox(const ChannelArgs &a, void *stream);
+// The patch kernel behind it, as launch_bias_patch.
+int launch_bias_patch_philox(const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, const ChannelArgs &a,
+                             void *stream);
 
 // launch_channel / launch_bias_patch on either source (the caller has checked `source`)
-inline int launch_channel_src(int source, int64_t seed, int64_t first_frame, int frames, int n, double snr, double sigma,
-                              int frac_bits, const uint8_t *cw, int cw_per_frame, void *out, int out_type, int *overflow,
-                              void *stream) {
-    return (source == FPLDPC_NOISE_PHILOX ? launch_channel_philox : launch_channel)(
-        seed, first_frame, frames, n, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow, stream);
+inline int launch_channel_src(int source, const ChannelArgs &a, void *stream) {
+    if (source == FPLDPC_NOISE_PHILOX) return launch_channel_philox(a, stream);
+    return launch_channel(a.seed, a.first_frame, a.frames, a.n, a.snr, a.sigma, a.frac_bits, a.cw, a.cw_per_frame, a.out,
+                          a.out_type, a.overflow, stream);
 }
-inline int launch_bias_patch_src(int source, const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift, int64_t seed,
-                                 int64_t first_frame, int frames, double snr, double sigma, int frac_bits, const uint8_t *cw,
-                                 int cw_per_frame, void *out, int out_type, int *overflow, double *logw, void *stream) {
-    return (source == FPLDPC_NOISE_PHILOX ? launch_bias_patch_philox : launch_bias_patch)(
-        b, d_pos, d_shift, seed, first_frame, frames, snr, sigma, frac_bits, cw, cw_per_frame, out, out_type, overflow, logw,
-        stream);
+inline int launch_bias_patch_src(int source, const fpldpc_bias &b, const int32_t *d_pos, const double *d_shift,
+                                 const ChannelArgs &a, void *stream) {
+    return (source == FPLDPC_NOISE_PHILOX ? launch_bias_patch_philox : launch_bias_patch)(b, d_pos, d_shift, a, stream);
 }
 
 }  // namespace fpldpc

@@ -162,6 +162,43 @@ def test_argument_rules(F):
         F.channel_llr(1, 0, 1, 25, SNR, SIGMA, source=1)
 
 
+PHILOX_RANGE = b"bad channel arguments (philox: 0 <= seed, first_frame + frames < 2^63)"
+# rule -> (the argument it breaks, the message): the rules are written once (philox_rules, fpldpc_source.hpp) for the
+# host twins and the device entry points; the host entry points report each with the status and message they always had
+PHILOX_RULES = {"null out": (dict(out=None), PHILOX_RANGE),
+                "n <= 0": (dict(n=0), PHILOX_RANGE),
+                "frac_bits 25": (dict(frac_bits=25), PHILOX_RANGE),
+                "negative seed": (dict(seed=-1), PHILOX_RANGE),
+                "frame range overflow": (dict(first=2**63 - 2, frames=2), PHILOX_RANGE),
+                "negative frames": (dict(frames=-1), PHILOX_RANGE),
+                "bad out_type": (dict(out_type=77), b"bad out_type"),
+                "bad cw_per_frame": (dict(cw_per_frame=2), b"cw_per_frame must be 0 or 1")}
+
+
+@pytest.mark.parametrize("rule", list(PHILOX_RULES))
+def test_philox_rule_status_and_message(F, rule):
+    L = F.lib()
+    buf, logw = np.empty((2, 25), np.int32), np.empty(2)
+    change, message = PHILOX_RULES[rule]
+    a = dict(seed=5, first=0, frames=1, n=25, frac_bits=4, out=buf.ctypes.data_as(ctypes.c_void_p), out_type=F.FPLDPC_LLR_I32,
+             cw_per_frame=0)
+    a.update(change)
+    bias = F.Bias(25, [3], [0.5])
+    if "cw_per_frame" not in change:  # the plain channel has no such argument
+        assert L.fpldpc_channel_llr_src_host(F.FPLDPC_NOISE_PHILOX, a["seed"], a["first"], a["frames"], a["n"], SNR, SIGMA,
+                                             a["frac_bits"], None, a["out"], a["out_type"], 1) == -1  # FPLDPC_ERR_ARG
+        assert L.fpldpc_last_error() == message
+    if "n" not in change:  # the shifted channel's n is its bias's
+        assert L.fpldpc_bias_channel_llr_src_host(bias._h, F.FPLDPC_NOISE_PHILOX, a["seed"], a["first"], a["frames"], SNR, SIGMA,
+                                                  a["frac_bits"], None, a["cw_per_frame"], a["out"], a["out_type"],
+                                                  logw.ctypes.data_as(ctypes.c_void_p), 1) == -1
+        assert L.fpldpc_last_error() == message
+    # the rules come after the source and, for the shifted channel, after the bias
+    assert L.fpldpc_bias_channel_llr_src_host(None, F.FPLDPC_NOISE_PHILOX, a["seed"], a["first"], a["frames"], SNR, SIGMA,
+                                              a["frac_bits"], None, a["cw_per_frame"], a["out"], a["out_type"], None, 1) == -1
+    assert L.fpldpc_last_error() == b"bias: null bias"
+
+
 @pytest.mark.parametrize("n,first", [(25, 0), (169, 2**33 + 5), (2209, 37)])
 def test_shifted_host_channel(F, n, first):
     frames, seed = 6, 2**40 + 7
